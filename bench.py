@@ -105,6 +105,10 @@ def main():
                     "from HOST memory - decoded uint8 frames (320x240, pinned) + teacher features go H2D on a copy stream, the GPU frame "
                     "transform (Resize 256 / crop 224 / flip / ToTensor, video_transform.py) runs there too, overlapped with the previous "
                     "episode's compute (trainwandb.py:419-443, video_reader.py:474-485); reported under `stream_inputs`, never as `value`")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps write what the timed path computed in its "
+                    "last step as DIR/<name>.npy (rank 0): the episode's loss and accuracy, a fixed seeded sample of the trained weights and of "
+                    "the accumulated gradient, the student's BatchNorm running statistics (dump_outputs below).  The priming then runs all "
+                    "--prime episodes, so that runs with the same arguments compare output for output")
     ap.add_argument("--emulate-world", type=int, default=0, help="single-GPU rehearsal of the per-rank cadence of a W-rank run: the optimizer "
                     "step (+ weight re-pack) every tasks_per_batch / W episodes; no collective runs, `value` stays the 1-GPU figure of that cadence")
     a = ap.parse_args()
@@ -204,7 +208,7 @@ def main():
         while i < n:
             k = min(every - ((it + 1) % every), n - i) or every      # up to the next optimizer step
             k = min(k, n - i)
-            g.run_interval([pool[(it + j) % len(pool)] for j in range(k)])      # by the global episode count: the same interval comes round
+            state["last"] = g.run_interval([pool[(it + j) % len(pool)] for j in range(k)])      # by the global episode count: the same interval comes round
             i += k
             it += k
             if (it + 1) % every == 0:
@@ -228,20 +232,21 @@ def main():
             graphed = graph_runner()
             if (it + 1) % every == 0 and graphed is None:
                 opt.expect_step()                      # world > 1: the bucket's tail is all-reduced under this episode's backward pass (pipelined: it runs in the flush below)
+            # state["last"]: what the caller receives for the most recent episode whose backward pass has been queued (--dump-outputs)
             if pipe is not None and state.get("pipe", True):
-                pipe.push(ep)
+                state["last"] = pipe.push(ep) or state.get("last")
             elif graphed is not None:
-                graphed(ep)
+                state["last"] = graphed(ep)
             else:
-                TL.train_task(ep, student, teacher, distiller, aggregate_accuracy, cfg)
+                state["last"] = TL.train_task(ep, student, teacher, distiller, aggregate_accuracy, cfg)
             if (it + 1) % every == 0:
                 if pipe is not None:
-                    pipe.flush()                       # the step needs the gradients of every episode up to this one
+                    state["last"] = pipe.flush() or state.get("last")       # the step needs the gradients of every episode up to this one
                 opt.step()
                 opt.zero_grad()
             sch.step()
         if pipe is not None:
-            pipe.flush()
+            state["last"] = pipe.flush() or state.get("last")
         return it
 
     def fence():
@@ -289,8 +294,8 @@ def main():
                     dist.all_reduce(flag, op=dist.ReduceOp.MIN)
                     still = int(flag.item())
                 quiet = quiet + 1 if still else 0
-                if quiet >= 3:
-                    break
+                if quiet >= 3 and not a.dump_outputs:      # --dump-outputs: always --prime episodes, so that the state the timed steps start
+                    break                                   # from depends on the arguments alone, not on when the allocator settled
         it = run(max(a.warmup, 2 * len(pool) + 1) if use_graph else a.warmup, it)
     fence()
     ops.CONV_TIMING = None if (use_graph or os.environ.get("LMKD_TIMED_EVENTS", "1") == "0") else []      # per-launch HIP events cannot be recorded into a captured graph (roofline_pass below times them)
@@ -304,6 +309,8 @@ def main():
     dt = time.perf_counter() - t0
     mallocs_timed = (torch.cuda.memory_stats(dev).get("num_device_alloc", 0) - mallocs0) if dev.type == "cuda" else 0
     opt_steps_timed = opt.steps - steps0             # read HERE: the repeat and host-idle passes below step the optimizer too
+    if a.dump_outputs and rank == 0:                 # before the repeat pass below trains on
+        dump_outputs(a.dump_outputs, state.get("last"), opt.bucket, student)
     timed_events, ops.CONV_TIMING = (ops.CONV_TIMING or []), None
     # the same K steps once more, timed the same way (barrier + synchronize on both sides), WITHOUT the per-launch HIP events of the
     # roofline bookkeeping: reported as `repeat` (never as `value`) - two figures that agree say the timed region was undisturbed
@@ -576,6 +583,31 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def dump_outputs(out_dir, last, bucket, student, sample=1 << 22, seed=20240):
+    """--dump-outputs: what the timed path computed, read right after its last step (the device is idle), as float32 .npy files:
+    loss / accuracy of the last episode (what train_task returns), a sample of `sample` flat indices - fixed by `seed`, the same in every
+    run - of the weights (bucket.flat, 22.7 M floats for the default student) and of the gradient accumulated since the last optimizer
+    step (grad + the side streams' shadow), and the student's BatchNorm running statistics in state_dict order.  32 MB in all."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+
+    def save(name, t):
+        np.save(os.path.join(out_dir, name + ".npy"), torch.as_tensor(t).detach().float().cpu().reshape(-1).numpy())
+    if last is not None:
+        if isinstance(last, list):      # a pipeline flush or a graphed interval: one result per episode, the last one is the step's
+            last = last[-1]
+        save("loss", last[0])
+        save("accuracy", last[1])
+    n = bucket.flat.numel()
+    idx = torch.randperm(n, generator=torch.Generator().manual_seed(seed))[:min(sample, n)].sort().values.to(bucket.flat.device)
+    save("weights_sample", bucket.flat[idx])
+    grad = bucket.grad if bucket.shadow is None else bucket.grad + bucket.shadow
+    save("grad_sample", grad[idx])
+    stats = [v.reshape(-1).float() for k, v in student.state_dict().items() if k.endswith(("running_mean", "running_var"))]
+    if stats:
+        save("bn_running_stats", torch.cat(stats))
 
 
 class HostEpisodes:

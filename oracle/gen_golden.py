@@ -1,4 +1,4 @@
-"""Generate tests/golden/*.npz by running the REFERENCE's own modules in the build
+"""Generate tests/golden/*.npz (and ref_train_flags.json) by running the REFERENCE's own modules in the build
 container, and check the oracle restatement (oracle/ref_cpu.py) against them.
 
 TEST INFRASTRUCTURE.  Runs only where /root/reference exists (the build container).
@@ -24,6 +24,7 @@ usage: python oracle/gen_golden.py [--check-only]
 """
 import argparse
 import importlib.util
+import json
 import os
 import sys
 import types
@@ -443,6 +444,19 @@ def trx_case_inputs(seed, ns, nq, shuffle):
     return p, sup1, qry1, sup2, qry2, lab
 
 
+def gen_train_flags():
+    """the `--flag` names of the reference's training parser (options.py up to parse_test_args: parse_common_args + parse_train_args)
+    and of its train_wandb.sh command line: names only (tests/test_host_cpu.py checks that the port's parser knows every one)"""
+    import re
+    out = {}
+    for f in ("options.py", "train_wandb.sh"):
+        txt = open(os.path.join(REF, f)).read()
+        if f == "options.py":
+            txt = txt[:txt.index("def parse_test_args")]
+        out[f] = sorted(set(re.findall(r"(--[a-z_]+)", txt)))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--check-only", action="store_true")
@@ -469,6 +483,16 @@ def main():
         else:
             np.savez_compressed(path, **data)
             print("wrote", path, "%.1f KB" % (os.path.getsize(path) / 1024))
+    path = os.path.join(GOLD, "ref_train_flags.json")
+    flags = gen_train_flags()
+    if a.check_only:
+        assert json.load(open(path)) == flags, path
+        print("checked", path)
+    else:
+        with open(path, "w") as f:
+            json.dump(flags, f, indent=1)
+            f.write("\n")
+        print("wrote", path)
 
 
 if __name__ == "__main__":

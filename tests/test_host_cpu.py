@@ -1,5 +1,6 @@
 """CPU tests: C-ABI library loads and exports every symbol of include/lmkd.h, registry / state_dict
 surface, loop semantics (with stand-in models), flat gradient bucket + gloo all-reduce (world_size 2)."""
+import json
 import os
 import subprocess
 import sys
@@ -315,7 +316,7 @@ _TRAIN_WANDB_SH = ("--dataset hmdb --shot 5 --debug False --num_gpus 1 --mode hm
                    "--distill_name fc_2_sup_dist --temp_set 2 --trans_linear_in_dim 2048")
 
 
-def test_train_cli_parses_the_reference_command_line():
+def test_train_cli_parses_the_reference_command_line(golden_dir):
     """python -m litemkd_amd.train takes the flags of options.py:7-76 under their own names: train_wandb.sh's command line parses
     unchanged, and every option the reference's parser declares exists here with the reference's default (plugin names excepted)"""
     from litemkd_amd import train as T
@@ -340,17 +341,13 @@ def test_train_cli_parses_the_reference_command_line():
     assert T.schedule_from_args(p.parse_args(["--dtype", "f32x3"])).conv_dtype == "fp32x3"
     assert T.schedule_from_args(p.parse_args(["--dtype", "bf16"])).act_dtype == "bf16"
     assert not T.schedule_from_args(p.parse_args(["--dtype", "f32native"])).merge_trunk_calls
-    # when the reference tree is at hand (the build container), every `--flag` its parser and its script name is known here
-    ref = "/root/reference"
-    if os.path.isdir(ref):
-        import re
-        known = set(p._option_string_actions)
-        for f in ("options.py", "train_wandb.sh"):
-            txt = open(os.path.join(ref, f)).read()
-            if f == "options.py":      # the training parser: parse_common_args + parse_train_args
-                txt = txt[:txt.index("def parse_test_args")]
-            for flag in re.findall(r"(--[a-z_]+)", txt):
-                assert flag in known, (f, flag)
+    # every `--flag` the reference's training parser and its script name is known here (names stored by oracle/gen_golden.py)
+    known = set(p._option_string_actions)
+    ref_flags = json.load(open(os.path.join(golden_dir, "ref_train_flags.json")))
+    assert set(ref_flags) == {"options.py", "train_wandb.sh"} and len(ref_flags["options.py"]) > 30
+    for f, flags in ref_flags.items():
+        for flag in flags:
+            assert flag in known, (f, flag)
     with pytest.raises(SystemExit):
         T.args_check(p.parse_args([]))          # "need to specify a checkpoint dir" (options.py:89-91)
 
