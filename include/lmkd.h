@@ -266,6 +266,45 @@ long lmkd_colsum_workspace(int C);
 int lmkd_colsum(const float* a, const float* b, float* out, long rows, int C, int accumulate, void* workspace, unsigned* tickets,
                 void* stream);
 
+/* ---- MobileNetV3-Large student trunk: the `mobile` module = torchvision mobilenet_v3_large().features of
+ * model/backbone/moblienetv3.py:26-31,60-65 (mobile_large_2fc) and :94-99,105-106 (mobile_large); csrc/mobile.hip.
+ * NHWC fp32, C % 8 == 0, plain fp32 arithmetic, deterministic fixed-order reductions.  The 1x1 convolutions are lmkd_gemm_f32 calls;
+ * their BatchNorm partial sums come from lmkd_col_stats.  BatchNorm tables are the [5][C] tables of lmkd_bn_finalize / lmkd_bn_eval_stats. */
+/* rows T of the [T][C][2] BatchNorm partial-sum buffer lmkd_dw_conv_fwd / lmkd_col_stats / lmkd_stem3x3_fwd fill for `pixels` output rows */
+long lmkd_mnv3_stat_tiles(long pixels);
+/* depthwise KxK convolution (InvertedResidual's groups = C conv), K in {3, 5}, stride in {1, 2}, pad (K-1)/2; w = the [C,1,K,K] weight.
+   x [N,H,W,C] -> y [N,Ho,Wo,C]; stat_partial (nullable) [lmkd_mnv3_stat_tiles(N*Ho*Wo)][C][2] per-tile (sum, sum of squares) of y */
+int lmkd_dw_conv_fwd(const float* x, const float* w, float* y, float* stat_partial, int N, int H, int W, int C, int K, int stride, void* stream);
+/* dx [N,H,W,C] from dy [N,Ho,Wo,C] (gather: one input element per lane) */
+int lmkd_dw_conv_bwd_data(const float* dy, const float* w, float* dx, int N, int H, int W, int C, int K, int stride, void* stream);
+long lmkd_dw_conv_bwd_weight_workspace(int N, int H, int W, int C, int K, int stride);
+/* dw [C,1,K,K] (+)= sum over frames and pixels of dy * x (per-workgroup partials + a fixed-order column reduction) */
+int lmkd_dw_conv_bwd_weight(const float* x, const float* dy, float* dw, void* workspace, long ws_bytes, int N, int H, int W, int C, int K,
+                            int stride, int accumulate, void* stream);
+/* BatchNorm partial sums of a [rows, C] tensor (a 1x1 convolution's GEMM output): stat_partial [lmkd_mnv3_stat_tiles(rows)][C][2] */
+int lmkd_col_stats(const float* x, float* stat_partial, long rows, int C, void* stream);
+/* y = act(x * scale + shift) (+ res): act 0 none, 1 ReLU, 2 Hardswish; res nullable (the InvertedResidual's shortcut, after the
+   project BatchNorm, which has no activation) */
+int lmkd_bn_act_fwd(const float* x, const float* stats, const float* res, float* y, long rows, int C, int act, void* stream);
+long lmkd_bn_act_bwd_workspace(long rows, int C);
+/* train-mode backward of lmkd_bn_act_fwd (its gradient w.r.t. res is dy itself): the activation's derivative is recomputed from x and the
+   table (Hardswish' as aten: 0 at x <= -3, x/3 + 1/2 on (-3, 3), 1 at x >= 3).  dparams [2][C] = (dbeta, dgamma), written */
+int lmkd_bn_act_bwd(const float* dy, const float* x, const float* stats, const float* gamma, float* dx, float* dparams, void* workspace,
+                    long ws_bytes, long rows, int C, int act, void* stream);
+/* squeeze-excitation (torchvision SqueezeExcitation): m [N,C] = mean over the HW pixels of a [N,HW,C]; y = a * s[n][c] */
+int lmkd_se_mean(const float* a, float* m, int N, int HW, int C, void* stream);
+int lmkd_se_scale_fwd(const float* a, const float* s, float* y, int N, int HW, int C, void* stream);
+/* ds (nullable) [N,C] = sum over HW of dy * a; da (nullable) = dy * s (+ dm[n][c] / HW when dm is given: the mean's gradient) */
+int lmkd_se_scale_bwd(const float* dy, const float* a, const float* s, const float* dm, float* da, float* ds, int N, int HW, int C, void* stream);
+int lmkd_hardsigmoid_fwd(const float* x, float* y, long n, void* stream);
+int lmkd_hardsigmoid_bwd(const float* dy, const float* x, float* dx, long n, void* stream);
+/* features.0: Conv 3 -> 16, 3x3, stride 2, pad 1 on the NHWC4 input [N,H,W,4]; w [16,3,3,3]; y [N,Ho,Wo,16];
+   stat_partial (nullable) [lmkd_mnv3_stat_tiles(N*Ho*Wo)][16][2] */
+int lmkd_stem3x3_fwd(const float* x4, const float* w, float* y, float* stat_partial, int N, int H, int W, void* stream);
+long lmkd_stem3x3_bwd_weight_workspace(int N, int H, int W);
+int lmkd_stem3x3_bwd_weight(const float* x4, const float* dy, float* dw, void* workspace, long ws_bytes, int N, int H, int W, int accumulate,
+                            void* stream);
+
 /* ---- matchers: TemporalCrossTransformer (TRX_2fcsup.py:74-148), SupportDK (:162-189), e_dist (e_dist_fc2.py:52-91) ---- */
 int lmkd_dropout_mask(float* mask, long n, float p, unsigned long long seed, void* stream);
 /* the same mask with the seed read from device memory when the kernel runs (hipGraph replays draw new masks) */

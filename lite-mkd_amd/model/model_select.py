@@ -7,7 +7,7 @@ import torch.nn as nn
 
 from .. import ops
 from . import classifiers
-from .backbone import resnet18_2fc, resnet18_student, resnet50_2fc, resnet50_stduent
+from .backbone import mobile_large, mobile_large_2fc, resnet18_2fc, resnet18_student, resnet50_2fc, resnet50_stduent
 
 # every key of the reference's name2backbone (model_select.py:167-180); None = plugin outside the hot path
 name2backbone = {
@@ -19,8 +19,8 @@ name2backbone = {
     "strmbackbone": None,
     "meta_baseline": None,
     "meta_baseline_fc2": None,
-    "moblienetv3_fc2": None,
-    "moblienetv3": None,
+    "moblienetv3_fc2": mobile_large_2fc,
+    "moblienetv3": mobile_large,
 }
 
 # model_select.py:182-199

@@ -2311,3 +2311,265 @@ def get_plan(support_labels, way):
             _PLANS_BY_CPU[(id(src), src._version, way)] = (weakref.ref(src), plan)
     _plan_cache[0], _plan_cache[1], _plan_cache[2] = support_labels, way, plan
     return plan
+
+
+# ------------------------------------------------------------------------------------------
+# MobileNetV3-Large student trunk (model/backbone/moblienetv3.py: torchvision mobilenet_v3_large().features; csrc/mobile.hip)
+# ------------------------------------------------------------------------------------------
+MNV3_BN_EPS = 1e-3          # torchvision mobilenet_v3_large: BatchNorm2d(eps=0.001, momentum=0.01) everywhere
+MNV3_BN_MOMENTUM = 0.01
+ACT_NONE, ACT_RELU, ACT_HARDSWISH = 0, 1, 2
+
+
+def _mnv3_chk(*tensors):
+    if _ACT_DTYPE[0] is not torch.float32:
+        raise RuntimeError("the MobileNetV3 backbone runs fp32 activations only; set_activation_dtype('%s') is not supported for it"
+                           % get_activation_dtype())
+    _chk(*tensors)      # (C % 8 == 0 and the shapes: checked by the entry points themselves)
+
+
+def _mnv3_bn_stats(part, count, bn, training, updates):
+    """[5][C] BatchNorm table: train mode from the partial sums `part` ([T][C][2]) of `count` elements per channel, the running-statistics
+    update (rm, rv, num_batches_tracked, stats) appended to `updates` (mnv3_running_update applies it); eval mode from the running
+    statistics"""
+    gamma, beta, rm, rv, nbt = bn
+    C = gamma.shape[0]
+    stats = _empty((5, C), gamma)
+    if training:
+        scratch = torch.empty(64 * 2 * C, dtype=torch.float64, device=gamma.device)
+        lib().call("lmkd_bn_finalize", _p(part), part.shape[0], C, count, _p(gamma), _p(beta), None, None, _f32(0.0), _f32(MNV3_BN_EPS),
+                   _p(stats), _p(scratch), _p(_tickets(part)), _stream(), None)
+        if updates is not None:
+            updates.append((rm, rv, nbt, stats))
+    else:
+        lib().call("lmkd_bn_eval_stats", C, _p(gamma), _p(beta), _p(rm), _p(rv), _f32(MNV3_BN_EPS), _p(stats), _stream())
+    return stats
+
+
+def mnv3_running_update(first, second):
+    """running mean / var (momentum 0.01) and num_batches_tracked of every BatchNorm of the trunk in ONE launch: first = the updates of the
+    support-frame call, second = the query-frame call's (same layers, same order; may be empty), applied in the reference's order"""
+    if not first:
+        return
+    if second and len(second) != len(first):
+        raise ValueError("the two trunk calls saw different BatchNorm layers")
+    n = len(first)
+    P = ctypes.c_void_p * n
+    rm = P(*[_pw(e[0]) for e in first])
+    rv = P(*[_pw(e[1]) for e in first])
+    s0 = P(*[_pw(e[3]) for e in first])
+    s1 = P(*[(_pw(second[i][3]) if second else None) for i in range(n)])
+    nbt = P(*[_pw(e[2]) for e in first])
+    C = (ctypes.c_int * n)(*[e[0].shape[0] for e in first])
+    lib().call("lmkd_bn_running_update_multi_nbt", rm, rv, s0, s1, nbt, C, n, _f32(MNV3_BN_MOMENTUM), _stream())
+
+
+def mnv3_bn_act(x, stats, act, res=None):
+    C = x.shape[-1]
+    y = torch.empty_like(x)
+    _mnv3_chk(x, stats, res)
+    lib().call("lmkd_bn_act_fwd", _p(x), _p(stats), _p(res), _p(y), x.numel() // C, C, int(act), _stream())
+    return y
+
+
+def mnv3_bn_act_bwd(dy, x, stats, gamma, act):
+    """train-mode backward of mnv3_bn_act -> dx, dgamma, dbeta"""
+    C = x.shape[-1]
+    rows = x.numel() // C
+    _mnv3_chk(dy, x, stats, gamma)
+    dx = torch.empty_like(x)
+    dparams = _empty((2, C), x)
+    ws = torch.empty(lib().value("lmkd_bn_act_bwd_workspace", rows, C), dtype=torch.uint8, device=x.device)
+    lib().call("lmkd_bn_act_bwd", _p(dy), _p(x), _p(stats), _p(gamma), _p(dx), _p(dparams), _p(ws), ws.numel(), rows, C, int(act), _stream())
+    return dx, dparams[1], dparams[0]
+
+
+def _stat_part(rows, C, like, training):
+    return _empty((lib().value("lmkd_mnv3_stat_tiles", rows), C, 2), like) if training else None
+
+
+_ONES = {}
+
+
+def _mnv3_pw_wgrad(dc, x, rows, Cout, Cin, shape):
+    """dW = dc^T @ x of a 1x1 convolution: K = rows runs to 400 x 112^2, and the GEMM's workgroups tile only the small Cout x Cin output.
+    The rows are split into S slices as a strided batch (S partial products [S][Cout][Cin]), then the slices are added by a second GEMM
+    ones[1, S] @ partials[S, Cout Cin] (ones are exact in every arithmetic mode): fixed order, deterministic."""
+    S = next((s for s in (64, 32, 16, 8, 4) if rows % s == 0 and rows // s >= 256), 1)
+    dw = _empty(shape, x)
+    if S == 1:
+        return gemm("M", "N", Cout, Cin, rows, dc, Cout, x, Cin, dw, Cin)
+    R = rows // S
+    part = _empty((S, Cout, Cin), x)
+    gemm("M", "N", Cout, Cin, R, dc, Cout, x, Cin, part, Cin, batch=S, sA=R * Cout, sB=R * Cin, sC=Cout * Cin)
+    key = (x.device.index, S)
+    ones = _ONES.get(key)
+    if ones is None:
+        ones = _ONES[key] = torch.ones(S, dtype=torch.float32, device=x.device)
+    gemm("K", "N", 1, Cout * Cin, S, ones, S, part, Cout * Cin, dw, Cout * Cin)
+    return dw
+
+
+class MnvStemFn(torch.autograd.Function):
+    """features.0: Conv2d(3, 16, 3, stride 2, pad 1, no bias) + BatchNorm + Hardswish.  Input NCHW [F, 3, H, W] (the reference's frame
+    layout, moved to NHWC4 here) or NHWC4; output NHWC [F, Ho, Wo, 16]"""
+
+    @staticmethod
+    def forward(ctx, x, w, gamma, beta, rm, rv, nbt, training, updates):
+        _mnv3_chk(x, w)
+        if x.dim() == 4 and x.shape[-1] == 4 and x.shape[1] != 3:
+            x4 = x.contiguous()                      # already NHWC4 (frames_u8_to_nhwc4)
+        else:
+            if x.dim() != 4 or x.shape[1] != 3:
+                raise RuntimeError("MobileNetV3 stem expects 3-channel frames, NCHW or NHWC4")
+            F_, _, H, W = x.shape
+            x4 = _empty((F_, H, W, 4), x)
+            lib().call("lmkd_nchw3_to_nhwc4", _p(x.contiguous()), _p(x4), F_, H, W, _stream(), None)
+        N, H, W, Cs = x4.shape
+        if tuple(w.shape) != (16, 3, 3, 3):
+            raise RuntimeError("MnvStemFn: a [16, 3, 3, 3] weight expected")
+        Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+        c = _empty((N, Ho, Wo, 16), x4)
+        part = _stat_part(N * Ho * Wo, 16, x4, training)
+        lib().call("lmkd_stem3x3_fwd", _p(x4), _p(w.contiguous()), _p(c), _p(part), N, H, W, _stream())
+        stats = _mnv3_bn_stats(part, N * Ho * Wo, (gamma, beta, rm, rv, nbt), training, updates)
+        ctx.training = training
+        ctx.save_for_backward(x4, c, stats, gamma)
+        return mnv3_bn_act(c, stats, ACT_HARDSWISH)
+
+    @staticmethod
+    def backward(ctx, dy):
+        _audit.engine_owned(dy)
+        if not ctx.training:
+            raise RuntimeError("MobileNetV3 backbone: backward through eval-mode BatchNorm is not supported")
+        x4, c, stats, gamma = ctx.saved_tensors
+        dc, dgamma, dbeta = mnv3_bn_act_bwd(dy.contiguous(), c, stats, gamma, ACT_HARDSWISH)
+        N, H, W, _ = x4.shape
+        dw = _empty((16, 3, 3, 3), x4)
+        ws = torch.empty(lib().value("lmkd_stem3x3_bwd_weight_workspace", N, H, W), dtype=torch.uint8, device=x4.device)
+        lib().call("lmkd_stem3x3_bwd_weight", _p(x4), _p(dc), _p(dw), _p(ws), ws.numel(), N, H, W, 0, _stream())
+        return None, dw, dgamma, dbeta, None, None, None, None, None
+
+
+class MnvConvBNActFn(torch.autograd.Function):
+    """Conv2dNormActivation of an InvertedResidual / features.16: y = act(BatchNorm(conv(x))) (+ res).
+    spec = (kind, K, stride, act): kind 'pw' = 1x1 convolution as a GEMM [N H W, Cin] x [Cout, Cin]^T on lmkd_gemm_f32 (+ lmkd_col_stats for
+    the BatchNorm's partial sums); kind 'dw' = depthwise K x K convolution (lmkd_dw_conv_*, statistics in its epilogue).
+    res (nullable): the block's shortcut, added after the project BatchNorm (act must be none)."""
+
+    @staticmethod
+    def forward(ctx, x, w, gamma, beta, rm, rv, nbt, res, spec, training, updates):
+        kind, K, stride, act = spec
+        x = x.contiguous()
+        _mnv3_chk(x, w, res)
+        N, H, W, Cin = x.shape
+        Cout = w.shape[0]
+        w = w.contiguous()
+        if kind == "pw":
+            rows = N * H * W
+            c = _empty((N, H, W, Cout), x)
+            gemm("K", "K", rows, Cout, Cin, x, Cin, w, Cin, c, Cout)
+            part = _stat_part(rows, Cout, x, training)
+            if training:
+                lib().call("lmkd_col_stats", _p(c), _p(part), rows, Cout, _stream())
+        elif kind == "dw":
+            if Cout != Cin or tuple(w.shape[1:]) != (1, K, K):
+                raise RuntimeError("MnvConvBNActFn: depthwise weight [C, 1, K, K] expected, got %s" % (tuple(w.shape),))
+            pad = (K - 1) // 2
+            Ho, Wo = (H + 2 * pad - K) // stride + 1, (W + 2 * pad - K) // stride + 1
+            rows = N * Ho * Wo
+            c = _empty((N, Ho, Wo, Cout), x)
+            part = _stat_part(rows, Cout, x, training)
+            lib().call("lmkd_dw_conv_fwd", _p(x), _p(w), _p(c), _p(part), N, H, W, Cin, K, stride, _stream())
+        else:
+            raise ValueError(kind)
+        if res is not None and (act != ACT_NONE or res.shape != c.shape):
+            raise RuntimeError("MnvConvBNActFn: the residual add follows a BatchNorm without activation, same shape")
+        stats = _mnv3_bn_stats(part, rows, (gamma, beta, rm, rv, nbt), training, updates)
+        ctx.spec, ctx.training, ctx.has_res = spec, training, res is not None
+        ctx.save_for_backward(x, w, c, stats, gamma)
+        return mnv3_bn_act(c, stats, act, res)
+
+    @staticmethod
+    def backward(ctx, dy):
+        _audit.engine_owned(dy)
+        if not ctx.training:
+            raise RuntimeError("MobileNetV3 backbone: backward through eval-mode BatchNorm is not supported")
+        kind, K, stride, act = ctx.spec
+        x, w, c, stats, gamma = ctx.saved_tensors
+        dy = dy.contiguous()
+        dc, dgamma, dbeta = mnv3_bn_act_bwd(dy, c, stats, gamma, act)
+        N, H, W, Cin = x.shape
+        Cout = w.shape[0]
+        dx = dw = None
+        if kind == "pw":
+            rows = N * H * W
+            if ctx.needs_input_grad[0]:
+                dx = _empty((N, H, W, Cin), x)
+                gemm("K", "N", rows, Cin, Cout, dc, Cout, w, Cin, dx, Cin)          # dx = dc @ W
+            if ctx.needs_input_grad[1]:
+                dw = _mnv3_pw_wgrad(dc, x, rows, Cout, Cin, tuple(w.shape))
+        else:
+            if ctx.needs_input_grad[0]:
+                dx = _empty((N, H, W, Cin), x)
+                lib().call("lmkd_dw_conv_bwd_data", _p(dc), _p(w), _p(dx), N, H, W, Cin, K, stride, _stream())
+            if ctx.needs_input_grad[1]:
+                dw = _empty(tuple(w.shape), x)
+                ws = torch.empty(lib().value("lmkd_dw_conv_bwd_weight_workspace", N, H, W, Cin, K, stride), dtype=torch.uint8, device=x.device)
+                lib().call("lmkd_dw_conv_bwd_weight", _p(x), _p(dc), _p(dw), _p(ws), ws.numel(), N, H, W, Cin, K, stride, 0, _stream())
+        dres = dy if ctx.has_res else None
+        return dx, dw, dgamma, dbeta, None, None, None, dres, None, None, None
+
+
+class MnvSEFn(torch.autograd.Function):
+    """torchvision SqueezeExcitation: y = a * hardsigmoid(fc2(relu(fc1(mean_hw(a))))), fc1 / fc2 = 1x1 convolutions with bias on [frames, C]
+    rows (GEMMs on lmkd_gemm_f32, bias and ReLU in the epilogue)"""
+
+    @staticmethod
+    def forward(ctx, a, w1, b1, w2, b2):
+        a = a.contiguous()
+        _mnv3_chk(a, w1, b1, w2, b2)
+        N, H, W, C = a.shape
+        Q = w1.shape[0]
+        HW = H * W
+        m = _empty((N, C), a)
+        lib().call("lmkd_se_mean", _p(a), _p(m), N, HW, C, _stream())
+        z1 = _empty((N, Q), a)
+        gemm("K", "K", N, Q, C, m, C, w1.contiguous(), C, z1, Q, bias=b1, relu=True)
+        z2 = _empty((N, C), a)
+        gemm("K", "K", N, C, Q, z1, Q, w2.contiguous(), Q, z2, C, bias=b2)
+        s = _empty((N, C), a)
+        lib().call("lmkd_hardsigmoid_fwd", _p(z2), _p(s), N * C, _stream())
+        y = torch.empty_like(a)
+        lib().call("lmkd_se_scale_fwd", _p(a), _p(s), _p(y), N, HW, C, _stream())
+        ctx.save_for_backward(a, m, z1, z2, s, w1, w2)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        _audit.engine_owned(dy)
+        a, m, z1, z2, s, w1, w2 = ctx.saved_tensors
+        dy = dy.contiguous()
+        N, H, W, C = a.shape
+        Q = w1.shape[0]
+        HW = H * W
+        ds = _empty((N, C), a)
+        lib().call("lmkd_se_scale_bwd", _p(dy), _p(a), _p(s), None, None, _p(ds), N, HW, C, _stream())
+        dz2 = _empty((N, C), a)
+        lib().call("lmkd_hardsigmoid_bwd", _p(ds), _p(z2), _p(dz2), N * C, _stream())
+        w1c, w2c = w1.contiguous(), w2.contiguous()
+        dw2 = _empty(tuple(w2.shape), a)
+        gemm("M", "N", C, Q, N, dz2, C, z1, Q, dw2, Q)                 # dW2 = dz2^T @ z1
+        db2 = colsum(dz2)
+        dz1 = _empty((N, Q), a)
+        gemm("K", "N", N, Q, C, dz2, C, w2c, Q, dz1, Q)                # dz1 = dz2 @ W2
+        g1 = _empty((N, Q), a)
+        lib().call("lmkd_relu_backward", _p(dz1), _p(z1), _p(g1), N * Q, _stream())
+        dw1 = _empty(tuple(w1.shape), a)
+        gemm("M", "N", Q, C, N, g1, Q, m, C, dw1, C)                   # dW1 = g1^T @ m
+        db1 = colsum(g1)
+        dm = _empty((N, C), a)
+        gemm("K", "N", N, C, Q, g1, Q, w1c, C, dm, C)                  # dm = g1 @ W1
+        da = torch.empty_like(a)
+        lib().call("lmkd_se_scale_bwd", _p(dy), _p(a), _p(s), _p(dm), _p(da), None, N, HW, C, _stream())
+        return da, dw1, db1, dw2, db2
