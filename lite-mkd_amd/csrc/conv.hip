@@ -31,7 +31,7 @@ struct ConvGemmArgs {
   int taps_pm1;               // conv_patch.h: every tap of every class lies within +-1 pixel (3x3 / 1x1 launches): the per-row tap masks come from a table
   int grid_step;              // persistent launches: gridDim.x (read from the argument block's LDS copy; gridDim itself is another scalar load from the segment)
   int grid_total;             // persistent launches (conv_patch.h): slots of the tile order, xcd_grid(n_rt, n_ct, xcd_mode); a workgroup walks slots blockIdx.x + k gridDim.x
-  int same;    // same-size convolution (conv_same_size): the tile height may be one only the patch kernel has
+  int same;    // (not read: the host plans same-size convolutions, plan_fwd / plan_dgrad; kept so the argument layout stays put)
   int halo;    // conv_patch_x3_kernel: largest |dh * Ws + dw| over the taps (pixels either side of the tile's own range)
   int accum;   // epilogue: out = acc + out (residual-branch gradient already sits in the output buffer)
   // STATS == 2 (inference): out = relu?( acc * scale[c] + shift[c] (+ res) ), scale/shift = rows 2/3 of the [5][C] BatchNorm table
@@ -646,41 +646,49 @@ extern "C" int lmkd_conv2d_pack_weights(const float* w_oihw, float* wp, int Cout
   return LMKD_OK;
 }
 
-// ---- compute dtype of the convolutions: 0 = exact fp32 MFMA, 1 = bf16 MFMA inputs with fp32 accumulation, 2 (DEFAULT since round 3:
-// the arithmetic bench.py's headline line runs) = fp32 as three bf16 planes, six products, 3 = nine products ----
-static int g_conv_bf16 = 0;
-static int g_conv_patch = 1;   // same-size convolutions of the bf16-plane modes from an LDS-resident patch (conv_patch.h); 0 = im2col gather
-extern "C" int lmkd_conv_set_patch(int on) { g_conv_patch = on ? 1 : 0; return LMKD_OK; }
-static int g_conv_x3 = 6;   // 0 | 6 | 9 bf16 MFMA products per fp32 product (conv_x3.h); library default: 6
-// mode 4: fp32 as TWO fp16 planes, three products (conv_patch16.h: h2_split4) in the trunk's convolution kernels - the 3x3 forward / data
+// ---- compute dtype of the convolutions (lmkd_conv_set_compute_dtype): 0 = exact fp32 MFMA, 1 = bf16 MFMA inputs with fp32 accumulation,
+// 2 (DEFAULT since round 3: the arithmetic bench.py's headline line runs) = fp32 as three bf16 planes, six products, 3 = nine products,
+// 4 = fp32 as TWO fp16 planes, three products (conv_patch16.h: h2_split4) in the trunk's convolution kernels - the 3x3 forward / data
 // gradient (conv_patch16_x3_kernel), the weight gradients (conv_wgrad_win16_kernel, conv_wgrad_x3_kernel, stem_wgrad_kernel), the stem's
 // forward (conv_stem_patch_kernel) - wherever the caller names the operands' maxima (lmkd_conv_operand_amax); every other launch (the
-// 1x1 forward, the inference epilogues, the loader-side BatchNorm), and every launch without them, runs mode 2.
-static int g_conv_h2 = 0;
+// 1x1 forward, the inference epilogues, the loader-side BatchNorm), and every launch without them, runs mode 2.  Read through conv_nprod only.
+static int g_conv_mode = 2;
 static std::atomic<long> g_h2_launches{0};       // launches that took the two-plane form (tests; the forward's thread and the autograd engine's both launch)
 static std::atomic<long> g_h2_fallbacks{0};      // mode-4 launches whose caller withheld a maximum because the range fence flagged the tensor (LMKD_AMAX_FENCED)
 extern "C" long lmkd_conv_h2_launches(void) { return g_h2_launches.load(); }
 extern "C" long lmkd_conv_h2_fallbacks(void) { return g_h2_fallbacks.load(); }
-static inline void note_fenced(const lmkd_amax_desc* am) { if (g_conv_h2 && am && (am->flags & LMKD_AMAX_FENCED)) ++g_h2_fallbacks; }
 extern "C" int lmkd_conv_set_compute_dtype(int mode) {
   LMKD_REQUIRE(mode >= 0 && mode <= 4, "lmkd_conv_set_compute_dtype: 0 fp32 MFMA, 1 bf16, 2 fp32 as 3xbf16 (6 products), 3 (9 products), 4 fp32 as 2xfp16 (3 products) over mode 2");
-  g_conv_bf16 = mode == 1;
-  g_conv_x3 = (mode == 2 || mode == 4) ? 6 : (mode == 3 ? 9 : 0);
-  g_conv_h2 = mode == 4;
+  g_conv_mode = mode;
   return LMKD_OK;
 }
-extern "C" int lmkd_conv_get_compute_dtype(void) { return g_conv_bf16 ? 1 : (g_conv_h2 ? 4 : (g_conv_x3 == 6 ? 2 : (g_conv_x3 == 9 ? 3 : 0))); }
+extern "C" int lmkd_conv_get_compute_dtype(void) { return g_conv_mode; }
+// MFMA products per fp32 product of a launch: 0 = the fp32 MFMA tile kernels (mode 0), 1 = one bf16 plane (mode 1; bf16 tensors, act16),
+// 6 / 9 = three bf16 planes (modes 2 / 3), 3 = two fp16 planes: mode 4, for a launch that has that form and the operands' maxima (`maxima`).
+// The only reader of the arithmetic mode.
+static inline int conv_nprod(bool act16 = false, bool maxima = false) {
+  if (act16) return 1;
+  switch (g_conv_mode) {
+    case 0: return 0;
+    case 1: return 1;
+    case 3: return 9;
+    case 4: return maxima ? 3 : 6;
+    default: return 6;
+  }
+}
+static inline bool conv_planes() { return conv_nprod() != 0; }      // modes 1 - 4: weights as bf16 planes in fragment order (conv_x3.h)
+static inline bool conv_h2() { return conv_nprod(false, true) == 3; }
+static inline void note_fenced(const lmkd_amax_desc* am) { if (conv_h2() && am && (am->flags & LMKD_AMAX_FENCED)) ++g_h2_fallbacks; }
 // The maxima of a launch's operands travel as explicit arguments (lmkd_amax_desc on the *_seg entry points; round 5 - before: one-shot
 // thread-local channels).  x_words / dy_words: device words holding the fp32 bits of max |x| / max |dy| per frame segment (upper bounds are
 // valid: a larger word costs range, not correctness), complete in stream order before the launch; either may be null; only mode 4 reads
 // them.  out_words (forward): the launch also folds max |y| into these words - in the epilogue of conv_patch16_x3_kernel, or by a
 // reduction pass of its own behind any other kernel - so that lmkd_bn_finalize_seg can bound relu(BatchNorm(y)) for a consumer that
 // applies the BatchNorm in its loader.
-static thread_local bool t_amax_recorded = false;      // (inside one call) set by the launch macros whose kernel folds ConvGemmArgs::amax_out
 // elements (16-bit) of the plane buffer of a packed weight of ncols x Kp in the current mode
 extern "C" long lmkd_conv2d_plane_elems(int ncols, int Kp) {
   const long n = (long)ncols * Kp;
-  return g_conv_bf16 ? n : (g_conv_h2 ? 18 * n + 32 : 12 * n);
+  return conv_nprod() == 1 ? n : (conv_h2() ? 18 * n + 32 : 12 * n);
 }
 // max |x| of n floats: slots = 0: into the ONE word at `word` (weight packs); slots = 1: into the slot words of one frame segment of an
 // activation maximum (lmkd_amax_next's layout: segment s at word + s * lmkd_amax_words() / 2).  The words are zeroed here first.
@@ -706,13 +714,13 @@ extern "C" int lmkd_conv2d_split_weights(const float* wp, void* wf, int ncols, i
   int grid = cdiv((long)ncols * Kp, 256);
   if (grid > 4096) grid = 4096;
   hipLaunchKernelGGL(split_weights_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, wp, (unsigned short*)wf, ncols, Kp,
-                     g_conv_bf16 ? 1 : 3);
+                     conv_nprod() == 1 ? 1 : 3);
   LMKD_CHECK_LAUNCH("split_weights_kernel");
-  if (!g_conv_bf16) {      // three-plane modes: the 16x16x32 fragment order behind the two 32x32x16 copies (conv_patch16.h)
+  if (conv_nprod() != 1) {      // three-plane modes: the 16x16x32 fragment order behind the two 32x32x16 copies (conv_patch16.h)
     hipLaunchKernelGGL(split_weights16_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, wp, (unsigned short*)wf + (long)ncols * Kp * 6, ncols, Kp);
     LMKD_CHECK_LAUNCH("split_weights16_kernel");
   }
-  if (g_conv_h2) {         // + the two fp16 planes (16x16x32 order) and max |w| behind them
+  if (conv_h2()) {         // + the two fp16 planes (16x16x32 order) and max |w| behind them
     unsigned short* wh = (unsigned short*)wf + (long)ncols * Kp * 12;
     const int rc = amax_impl(wp, (long)ncols * Kp, wh + (long)ncols * Kp * 4, 0, stream);
     if (rc) return rc;
@@ -824,11 +832,11 @@ __global__ void repack_multi_kernel(RepackArgs a) {
 // ws[i], wfs[i]: OIHW weight and destination planes of entry i; dims[i * 6 ..] = Cout, Cin, Cs, KH, KW, mode.  Modes 1-3 only.
 extern "C" int lmkd_conv2d_repack_multi(const float* const* ws, void* const* wfs, const int* dims, int n, void* stream) {
   LMKD_REQUIRE(ws && wfs && dims && n > 0, "lmkd_conv2d_repack_multi: null pointer");
-  LMKD_REQUIRE(g_conv_x3 || g_conv_bf16, "lmkd_conv2d_repack_multi: fragment-order planes exist in the bf16-plane modes only");
+  LMKD_REQUIRE(conv_planes(), "lmkd_conv2d_repack_multi: fragment-order planes exist in the bf16-plane modes only");
   for (int i0 = 0; i0 < n; i0 += LMKD_REPACK_MAX) {
     RepackArgs a;
     memset(&a, 0, sizeof(a));
-    a.npl = g_conv_bf16 ? 1 : 3;
+    a.npl = conv_nprod() == 1 ? 1 : 3;
     const int m = std::min(LMKD_REPACK_MAX, n - i0);
     long most = 0;
     for (int j = 0; j < m; ++j) {
@@ -848,7 +856,7 @@ extern "C" int lmkd_conv2d_repack_multi(const float* const* ws, void* const* wfs
     if (gx > 512) gx = 512;
     hipLaunchKernelGGL(repack_multi_kernel, dim3(gx, m), dim3(256), 0, (hipStream_t)stream, a);
     LMKD_CHECK_LAUNCH("repack_multi_kernel");
-    if (g_conv_h2) {
+    if (conv_h2()) {
       for (int phase = 0; phase < 3; ++phase) {
         hipLaunchKernelGGL(repack_h2_kernel, dim3(phase == 0 ? 1 : gx, m), dim3(256), 0, (hipStream_t)stream, a, phase);
         LMKD_CHECK_LAUNCH("repack_h2_kernel");
@@ -878,13 +886,13 @@ static inline int cfg_wg_per_cu(int id) { return id == 1 ? 2 : (id == 3 ? 4 : 3)
 // matrix-pipe bound, so what differs is how evenly the launch's tiles divide over the CUs (the tail).
 // same: same-size convolution served by the LDS-patch kernel (patch_eligible)
 static int pick_conv_cfg(long rows_per_class, int nclass, int ncols, bool same = false) {
-  if (g_conv_x3 || g_conv_bf16) {
+  if (conv_planes()) {
     if (g_tile_override >= 7) {
       int id = g_tile_override;
       if (id == 10 && !same) id = 8;
       if (id == 11 && !same) id = 9;
       if (id == 12 && !same) id = 8;
-      if ((id == 13 || id == 14) && (!same || !g_conv_bf16)) id = id == 13 ? 10 : 7;
+      if ((id == 13 || id == 14) && (!same || conv_nprod() != 1)) id = id == 13 ? 10 : 7;
       if (id == 10 && !same) id = 8;
       if (ncols <= 64 && cfg_bn(id) == 128) id = id == 10 ? 7 : (id == 12 ? 11 : (id == 13 ? 14 : 9));
       return id;
@@ -895,7 +903,7 @@ static int pick_conv_cfg(long rows_per_class, int nclass, int ncols, bool same =
       // 64x64: half the LDS reads per MFMA) in the three-plane modes once it gives every CU at least two rounds of tiles, 128x64 otherwise.
       if (ncols <= 64) return 11;
       const long t128 = cdiv(rows_per_class, 128) * cdiv(ncols, 128);
-      return (g_conv_x3 && t128 >= 1024) ? 12 : 11;      // one-plane modes: 128x64 throughout (three or four workgroups per CU)
+      return (conv_nprod() != 1 && t128 >= 1024) ? 12 : 11;      // one-plane modes: 128x64 throughout (three or four workgroups per CU)
     }
     if (ncols <= 64) return 9;
     // measured (tools/conv_bench_x3.py): 128x128 (one workgroup per CU) wins once the launch has a tile per CU
@@ -926,22 +934,6 @@ static int pick_conv_cfg(long rows_per_class, int nclass, int ncols, bool same =
   return best;
 }
 
-template <class Cfg, bool SMALLC, int STATS, bool BF16 = false>
-static void launch_conv_cfg(ConvGemmArgs a, int ncols, hipStream_t s) {
-  conv_set_tiles(a, Cfg::BM);
-  a.n_ct = cdiv(ncols, Cfg::BN);
-  a.xcd_mode = (a.n_ct >= 8 && (a.n_ct & 7) == 0) ? 1 : 0;
-  if (g_xcd_mode == 0) a.xcd_mode = 0;
-  const dim3 grid(xcd_grid(a.n_rt, a.n_ct, a.xcd_mode));
-  if constexpr (STATS == 1 && !SMALLC && !BF16) {      // the training forward of a conv that follows a BatchNorm + ReLU
-    if (a.pre_stats) {
-      hipLaunchKernelGGL((conv_gemm_kernel<Cfg, SMALLC, STATS, BF16, true>), grid, dim3(Cfg::THREADS), 0, s, a);
-      return;
-    }
-  }
-  hipLaunchKernelGGL((conv_gemm_kernel<Cfg, SMALLC, STATS, BF16>), grid, dim3(Cfg::THREADS), 0, s, a);
-}
-
 // hipFuncAttributeMaxDynamicSharedMemorySize of a kernel instance, once per (instance, device), from whichever host thread launches
 // first (the forward's thread and the autograd engine's both launch): `mask` is the instance's static bit set of devices done.
 static inline void lmkd_lds_attr_once(std::atomic<unsigned long long>& mask, const void* fn, int bytes) {
@@ -955,6 +947,11 @@ static inline void lmkd_lds_attr_once(std::atomic<unsigned long long>& mask, con
     return;
   }
   mask.fetch_or(bit, std::memory_order_release);
+}
+template <auto K>
+static inline void lds_attr_once(int bytes) {
+  static std::atomic<unsigned long long> mask{0};
+  lmkd_lds_attr_once(mask, reinterpret_cast<const void*>(K), bytes);
 }
 
 // Grid of a PERSISTENT launch (conv_patch.h): no more workgroups than the chip holds at once (occupancy of this instance with `lds` bytes of
@@ -974,16 +971,17 @@ static int lmkd_cu_count() {
 }
 static int g_conv_persist = 1;      // 0: one workgroup per slot of the tile order (the form before round 5; for A/B measurements)
 extern "C" int lmkd_conv_set_persistent(int on) { g_conv_persist = on ? 1 : 0; return LMKD_OK; }
-template <class K>
-static int persistent_grid(PersistOcc& c, K kernel, int threads, size_t lds, int total) {
+template <auto K>
+static int persistent_grid(int threads, size_t lds, int total) {
   if (!g_conv_persist) return total;
+  static PersistOcc c;
   int occ = 0;
   {
     std::lock_guard<std::mutex> lk(c.mu);
     const int n = c.n.load();
     for (int i = 0; i < n; ++i) if (c.lds[i] == (int)lds) occ = c.occ[i];
     if (!occ) {
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, threads, lds) != hipSuccess || occ < 1) occ = 1;
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, K, threads, lds) != hipSuccess || occ < 1) occ = 1;
       if (n < 8) { c.lds[n] = (int)lds; c.occ[n] = occ; c.n.store(n + 1); }
     }
   }
@@ -996,8 +994,10 @@ static int persistent_grid(PersistOcc& c, K kernel, int threads, size_t lds, int
 
 // Same-size convolutions (3x3 / stride 1 forward and data gradient, 1x1 / stride 1) of the bf16-plane modes read an LDS-resident
 // input patch (conv_patch.h).  Returns the halo (largest |dh * Ws + dw| over the taps), or -1 when the launch is not of that kind.
+static int g_conv_patch = 1;   // same-size convolutions of the bf16-plane modes from an LDS-resident patch (conv_patch.h); 0 = im2col gather
+extern "C" int lmkd_conv_set_patch(int on) { g_conv_patch = on ? 1 : 0; return LMKD_OK; }
 static int patch_halo(const ConvGemmArgs& a) {
-  if (!g_conv_patch || !(g_conv_x3 || g_conv_bf16) || a.Cs % 32 != 0 || a.sh != 1) return -1;
+  if (!g_conv_patch || !conv_planes() || a.Cs % 32 != 0 || a.sh != 1) return -1;
   // one class: output grid = input grid; four parity classes (stride-2 data gradient): each class runs on the dy grid
   const bool plain = a.nclass == 1 && a.Hs == a.Ho && a.Ws == a.Wo;
   const bool classes = a.nclass == 4 && a.Hr == a.Hs && a.Wr == a.Ws;
@@ -1043,244 +1043,381 @@ static inline int taps_within_one(const ConvGemmArgs& a) {
       if (a.taps[c][t].dh < -1 || a.taps[c][t].dh > 1 || a.taps[c][t].dw < -1 || a.taps[c][t].dw > 1) return 0;
   return 1;
 }
-template <class Cfg>
-static void launch_conv_patch(ConvGemmArgs a, int ncols, int halo, hipStream_t s) {
-  conv_set_tiles(a, Cfg::BM);
-  a.taps_pm1 = taps_within_one(a);
-  a.n_ct = cdiv(ncols, Cfg::BN);
-  a.xcd_mode = (a.n_ct >= 8 && (a.n_ct & 7) == 0) ? 1 : 0;
-  if (g_xcd_mode == 0) a.xcd_mode = 0;
-  const dim3 grid(xcd_grid(a.n_rt, a.n_ct, a.xcd_mode));
-  a.halo = halo;
-  const int npl = (g_conv_bf16 || g_lmkd_act_bf16) ? 1 : 3;
-  size_t lds = patch_lds_bytes(Cfg::BM, halo, npl);
-#define LMKD_PATCH(NPROD, PRE, IO)                                                                                             \
-  do {                                                                                                                         \
-    static std::atomic<unsigned long long> attr_done{0};                                                                       \
-    static PersistOcc pocc;                                                                                                    \
-    lmkd_lds_attr_once(attr_done, reinterpret_cast<const void*>(&conv_patch_x3_kernel<Cfg, NPROD, PRE, IO>),                   \
-                       (int)patch_lds_bytes(Cfg::BM, PATCH_HALO_MAX, NPROD == 1 ? 1 : 3));                                     \
-    a.grid_total = (int)grid.x;                                                                                                \
-    const dim3 pgrid(NPROD == 3 ? persistent_grid(pocc, conv_patch_x3_kernel<Cfg, NPROD, PRE, IO>, Cfg::THREADS, lds, a.grid_total) : a.grid_total); \
-    a.grid_step = (int)pgrid.x;                                                                                                \
-    hipLaunchKernelGGL((conv_patch_x3_kernel<Cfg, NPROD, PRE, IO>), pgrid, dim3(Cfg::THREADS), lds, s, a);                     \
-  } while (0)
-  if constexpr (Cfg::THREADS == 256 && Cfg::BM == 128) {      // the benchmark's tiles (ids 11 / 12) on the 16x16x32 MFMA (conv_patch16.h)
-    // (lmkd_conv_set_patch16; the inference epilogue - residual loads, no sums - stays on the 16x16x32 kernel and its 16-byte accesses: 168.7 vs 160.6 inference episodes/s)
-    const bool h2_on_32 = g_patch16 == 1 && Cfg::BN == 64 && a.Co <= 64 && g_conv_h2 && a.h2_xw && !a.src2 && !a.ep_stats;
-    if (g_patch16 && g_conv_x3 && !g_lmkd_act_bf16 && !h2_on_32) {
-#define LMKD_PATCH16(NPROD, PRE, EP)                                                                                           \
-  do {                                                                                                                         \
-    t_amax_recorded = true;                                                                                                    \
-    static std::atomic<unsigned long long> attr_done{0};                                                                       \
-    lmkd_lds_attr_once(attr_done, reinterpret_cast<const void*>(&conv_patch16_x3_kernel<Cfg, NPROD, PRE, EP>),                 \
-                       (int)patch_lds_bytes(Cfg::BM, PATCH_HALO_MAX, 3));                                                      \
-    hipLaunchKernelGGL((conv_patch16_x3_kernel<Cfg, NPROD, PRE, EP>), grid, dim3(Cfg::THREADS), lds, s, a);                    \
-  } while (0)
-      if (a.src2) {
-#define LMKD_PATCH16S(NPROD, EP)                                                                                               \
-  do {                                                                                                                         \
-    t_amax_recorded = true;                                                                                                    \
-    static std::atomic<unsigned long long> attr_done{0};                                                                       \
-    lmkd_lds_attr_once(attr_done, reinterpret_cast<const void*>(&conv_patch16_x3_kernel<Cfg, NPROD, false, EP, true>),         \
-                       (int)patch_lds_bytes(Cfg::BM, PATCH_HALO_MAX, 3));                                                      \
-    hipLaunchKernelGGL((conv_patch16_x3_kernel<Cfg, NPROD, false, EP, true>), grid, dim3(Cfg::THREADS), lds, s, a);            \
-  } while (0)
-        if (a.ep_stats) {
-          if (g_conv_x3 == 9) LMKD_PATCH16S(9, true);
-          else if (g_conv_h2 && a.h2_xw) { LMKD_PATCH16S(3, true); ++g_h2_launches; }      // inference in the two-plane arithmetic (round 5)
-          else LMKD_PATCH16S(6, true);
-        }
-        else if (g_conv_h2 && a.h2_xw) { LMKD_PATCH16S(3, false); ++g_h2_launches; }
-        else { if (g_conv_x3 == 9) LMKD_PATCH16S(9, false); else LMKD_PATCH16S(6, false); }
-#undef LMKD_PATCH16S
-        return;
-      }
-      if (a.ep_stats) {
-        if (g_conv_x3 == 9) LMKD_PATCH16(9, false, true);
-        else if (g_conv_h2 && a.h2_xw) { LMKD_PATCH16(3, false, true); ++g_h2_launches; }      // inference: BatchNorm affine (+ residual, ReLU) on the scaled accumulators; max |y| recorded in the same epilogue
-        else LMKD_PATCH16(6, false, true);
-      }
-      else if (a.pre_stats) {
-        if (g_conv_x3 == 9) LMKD_PATCH16(9, true, false);
-        else if (g_conv_h2 && a.h2_xw) { LMKD_PATCH16(3, true, false); ++g_h2_launches; }      // h2_xw: a bound of relu(BatchNorm(x)) (lmkd_bn_finalize_bound)
-        else LMKD_PATCH16(6, true, false);
-      }
-      else if (a.bnb_x) {      // data gradient with the BatchNorm-backward sums in its epilogue: instances of their own (conv_patch16.h, BNB)
-#define LMKD_PATCH16B(NPROD)                                                                                                   \
-  do {                                                                                                                         \
-    t_amax_recorded = true;                                                                                                    \
-    static std::atomic<unsigned long long> attr_done{0};                                                                       \
-    lmkd_lds_attr_once(attr_done, reinterpret_cast<const void*>(&conv_patch16_x3_kernel<Cfg, NPROD, false, false, false, true>), \
-                       (int)patch_lds_bytes(Cfg::BM, PATCH_HALO_MAX, 3));                                                      \
-    hipLaunchKernelGGL((conv_patch16_x3_kernel<Cfg, NPROD, false, false, false, true>), grid, dim3(Cfg::THREADS), lds, s, a);  \
-  } while (0)
-        if (g_conv_h2 && a.h2_xw) { LMKD_PATCH16B(3); ++g_h2_launches; }
-        else if (g_conv_x3 == 9) LMKD_PATCH16B(9);
-        else LMKD_PATCH16B(6);
-#undef LMKD_PATCH16B
-      }
-      else if (g_conv_h2 && a.h2_xw) { LMKD_PATCH16(3, false, false); ++g_h2_launches; }
-      else { if (g_conv_x3 == 9) LMKD_PATCH16(9, false, false); else LMKD_PATCH16(6, false, false); }
-#undef LMKD_PATCH16
-      return;
-    }
-  }
-  if (g_conv_h2 && a.h2_xw && !a.ep_stats && !g_lmkd_act_bf16) {      // two fp16 planes on v_mfma_f32_32x32x16_f16: the 64-column tile (lmkd_conv_set_patch16), or a tile conv_patch16_x3_kernel does not have
-    t_amax_recorded = true;      // (x3_epilogue<.., H2> folds ConvGemmArgs::amax_out)
-    lds = patch_lds_bytes(Cfg::BM, halo, 2);
-    if (a.pre_stats) LMKD_PATCH(3, true, 0); else LMKD_PATCH(3, false, 0);
-    ++g_h2_launches;
-    return;
-  }
-  if (a.ep_stats) {      // inference: BatchNorm affine (+ residual, ReLU) in the epilogue, fp32 tensors
-    if (g_conv_bf16) LMKD_PATCH(1, false, 4);
-    else if (g_conv_x3 == 9) LMKD_PATCH(9, false, 4);
-    else LMKD_PATCH(6, false, 4);
-  } else if (g_lmkd_act_bf16) LMKD_PATCH(1, false, 3);
-  else if (a.pre_stats) {
-    if (g_conv_bf16) LMKD_PATCH(1, true, 0);
-    else if (g_conv_x3 == 9) LMKD_PATCH(9, true, 0);
-    else LMKD_PATCH(6, true, 0);
-  } else {
-    if (g_conv_bf16) LMKD_PATCH(1, false, 0);
-    else if (g_conv_x3 == 9) LMKD_PATCH(9, false, 0);
-    else LMKD_PATCH(6, false, 0);
-  }
-#undef LMKD_PATCH
-}
 
-// (round 4: conv_patch16_x3_kernel on 256 x 64 tiles - four waves stacked over the rows, wave tiles 64 x 64, two workgroups per CU - was
-// built as tile id 15 and measured SLOWER than id 11 on every layer, 443 vs 383 us on layer 1 in fp32h2: profiles/r04_tile_ab.txt; removed)
-// one-plane modes only (tile ids 13 / 14: 256-row tiles with four waves)
-template <class Cfg>
-static void launch_conv_patch_1p(ConvGemmArgs a, int ncols, int halo, hipStream_t s) {
-  conv_set_tiles(a, Cfg::BM);
-  a.taps_pm1 = taps_within_one(a);
-  a.n_ct = cdiv(ncols, Cfg::BN);
-  a.xcd_mode = (a.n_ct >= 8 && (a.n_ct & 7) == 0) ? 1 : 0;
-  if (g_xcd_mode == 0) a.xcd_mode = 0;
-  const dim3 grid(xcd_grid(a.n_rt, a.n_ct, a.xcd_mode));
-  a.halo = halo;
-  const size_t lds = patch_lds_bytes(Cfg::BM, halo, 1);
-#define LMKD_PATCH1(PRE, IO)                                                                                                   \
-  do {                                                                                                                         \
-    static std::atomic<unsigned long long> attr_done{0};                                                                       \
-    lmkd_lds_attr_once(attr_done, reinterpret_cast<const void*>(&conv_patch_x3_kernel<Cfg, 1, PRE, IO>),                       \
-                       (int)patch_lds_bytes(Cfg::BM, PATCH_HALO_MAX, 1));                                                      \
-    a.grid_total = (int)grid.x;                                                                                                \
-    const dim3 pgrid(a.grid_total);      /* (one-plane instances: one workgroup per tile, conv_patch.h PERSIST) */            \
-    a.grid_step = (int)pgrid.x;                                                                                                \
-    hipLaunchKernelGGL((conv_patch_x3_kernel<Cfg, 1, PRE, IO>), pgrid, dim3(Cfg::THREADS), lds, s, a);                         \
-  } while (0)
-  if (a.ep_stats) LMKD_PATCH1(false, 4);
-  else if (g_lmkd_act_bf16) LMKD_PATCH1(false, 3);
-  else if (a.pre_stats) LMKD_PATCH1(true, 0);
-  else LMKD_PATCH1(false, 0);
-#undef LMKD_PATCH1
-}
-
-template <class Cfg, bool SMALLC, bool STATS>
-static void launch_conv_x3(ConvGemmArgs a, int ncols, hipStream_t s) {
-  conv_set_tiles(a, Cfg::BM);
-  a.n_ct = cdiv(ncols, Cfg::BN);
-  a.xcd_mode = (a.n_ct >= 8 && (a.n_ct & 7) == 0) ? 1 : 0;
-  if (g_xcd_mode == 0) a.xcd_mode = 0;
-  const dim3 grid(xcd_grid(a.n_rt, a.n_ct, a.xcd_mode));
-  // ONE instance serves launches with and without BatchNorm partials (stat_partial null -> nothing written): hipcc schedules the
-  // main loop of the instance without the statistics epilogue worse (register copies in front of the MFMAs: 105 vs 148 TFLOP/s
-  // on the same layer), so that instance is not built
-  (void)STATS;
-  if constexpr (!SMALLC) {
-    if (a.ep_stats) {      // inference epilogue (x3_epilogue EP): stride-2 / 1x1-downsample convolutions of an eval forward
-      if (g_conv_bf16) hipLaunchKernelGGL((conv_gemm_x3_kernel<Cfg, false, true, 1, false, 4>), grid, dim3(Cfg::THREADS), 0, s, a);
-      else if (g_conv_x3 == 9) hipLaunchKernelGGL((conv_gemm_x3_kernel<Cfg, false, true, 9, false, 4>), grid, dim3(Cfg::THREADS), 0, s, a);
-      else hipLaunchKernelGGL((conv_gemm_x3_kernel<Cfg, false, true, 6, false, 4>), grid, dim3(Cfg::THREADS), 0, s, a);
-      return;
-    }
-  }
-  if (g_lmkd_act_bf16) {      // bf16 tensors in HBM (one-plane mode): the loader copies, the epilogue rounds; the stem input stays fp32
-    if constexpr (SMALLC) hipLaunchKernelGGL((conv_gemm_x3_kernel<Cfg, true, true, 1, false, 2>), grid, dim3(Cfg::THREADS), 0, s, a);
-    else hipLaunchKernelGGL((conv_gemm_x3_kernel<Cfg, false, true, 1, false, 3>), grid, dim3(Cfg::THREADS), 0, s, a);
-    return;
-  }
-  if constexpr (!SMALLC) {
-    if (a.pre_stats) {      // training forward fed by relu(BatchNorm(raw)): normalise + rectify when the tile is stored to LDS
-      if (g_conv_bf16) hipLaunchKernelGGL((conv_gemm_x3_kernel<Cfg, false, true, 1, true>), grid, dim3(Cfg::THREADS), 0, s, a);
-      else if (g_conv_x3 == 9) hipLaunchKernelGGL((conv_gemm_x3_kernel<Cfg, false, true, 9, true>), grid, dim3(Cfg::THREADS), 0, s, a);
-      else hipLaunchKernelGGL((conv_gemm_x3_kernel<Cfg, false, true, 6, true>), grid, dim3(Cfg::THREADS), 0, s, a);
-      return;
-    }
-  }
-  if (g_conv_bf16) hipLaunchKernelGGL((conv_gemm_x3_kernel<Cfg, SMALLC, true, 1>), grid, dim3(Cfg::THREADS), 0, s, a);
-  else if (g_conv_x3 == 9) hipLaunchKernelGGL((conv_gemm_x3_kernel<Cfg, SMALLC, true, 9>), grid, dim3(Cfg::THREADS), 0, s, a);
-  else hipLaunchKernelGGL((conv_gemm_x3_kernel<Cfg, SMALLC, true, 6>), grid, dim3(Cfg::THREADS), 0, s, a);
-}
-
-template <bool SMALLC, int STATS>
-static int launch_conv_gemm(const ConvGemmArgs& a, int ncols, hipStream_t s) {
-  if constexpr (STATS != 2 || !SMALLC) {      // STATS == 2 (inference epilogue) exists on the bf16-plane kernels for Cs % 32 == 0
-    if (g_conv_x3 || g_conv_bf16) {      // bf16 planes in LDS, weights in fragment order (conv_x3.h): 1, 6 or 9 products
-      const int halo = SMALLC ? -1 : patch_halo(a);
-      int id = pick_conv_cfg(a.rows_per_class, a.nclass, ncols, a.same != 0);
-      if (halo < 0 && id == 10) id = 7;
-      if (halo < 0 && id == 11) id = 9;
-      if (halo < 0 && id == 12) id = 8;      // same tile height (the BatchNorm partials' row count) on the gather kernel
-      if (halo < 0 && (id == 13 || id == 14)) id = 7;
-      if (halo >= 0) {
-        switch (id) {
-          case 7: launch_conv_patch<X3Cfg<256, 64, 4, 2>>(a, ncols, halo, s); break;
-          case 8: launch_conv_patch<X3Cfg<128, 128, 2, 4>>(a, ncols, halo, s); break;
-          case 10: launch_conv_patch<X3Cfg<256, 128, 2, 4>>(a, ncols, halo, s); break;
-          case 11: launch_conv_patch<X3Cfg<128, 64, 2, 2, 3>>(a, ncols, halo, s); break;
-          case 12: launch_conv_patch<X3Cfg<128, 128, 2, 2, 2>>(a, ncols, halo, s); break;
-          case 13: launch_conv_patch_1p<X3Cfg<256, 128, 2, 2, 2>>(a, ncols, halo, s); break;
-          case 14: launch_conv_patch_1p<X3Cfg<256, 64, 2, 2, 2>>(a, ncols, halo, s); break;
-          default: launch_conv_patch<X3Cfg<128, 64, 4, 2>>(a, ncols, halo, s); break;
-        }
-        LMKD_CHECK_LAUNCH("conv_patch_x3_kernel");
-        return LMKD_OK;
-      }
-      switch (id) {
-        case 7: launch_conv_x3<X3Cfg<256, 64, 4, 2>, SMALLC, STATS == 1>(a, ncols, s); break;
-        case 8: launch_conv_x3<X3Cfg<128, 128, 2, 4>, SMALLC, STATS == 1>(a, ncols, s); break;
-        default: launch_conv_x3<X3Cfg<128, 64, 4, 2>, SMALLC, STATS == 1>(a, ncols, s); break;
-      }
-      LMKD_CHECK_LAUNCH("conv_gemm_x3_kernel");
-      return LMKD_OK;
-    }
-  }
-  switch (pick_conv_cfg(a.rows_per_class, a.nclass, ncols)) {
-    case 1: launch_conv_cfg<TileCfg<128, 128, 2, 2>, SMALLC, STATS>(a, ncols, s); break;
-    case 2: launch_conv_cfg<TileCfg<128, 64, 2, 2>, SMALLC, STATS>(a, ncols, s); break;
-    case 3: launch_conv_cfg<TileCfg<64, 64, 2, 2>, SMALLC, STATS>(a, ncols, s); break;
-    case 5: launch_conv_cfg<TileCfg<128, 128, 2, 4>, SMALLC, STATS>(a, ncols, s); break;
-    case 6: launch_conv_cfg<TileCfg<128, 64, 4, 2>, SMALLC, STATS>(a, ncols, s); break;
-    default: launch_conv_cfg<TileCfg<64, 128, 2, 2>, SMALLC, STATS>(a, ncols, s); break;
-  }
-  LMKD_CHECK_LAUNCH("conv_gemm_kernel");
-  return LMKD_OK;
-}
-
-// The stem (7x7 / stride 2 / pad 3 on the NHWC4 input, Cout <= 64) of the bf16-plane modes runs conv_stem_patch_kernel (conv_stem.h):
-// one workgroup per pair of output rows.  Returns the patch row pitch in pixels, or 0 when the launch is not of that kind.
 // stride-2 3x3 forward convolution as four same-size convolutions over the input's parity classes (conv_patch16.h, SRC2)?
 static bool fwd_s2_patch_ok(int N, int H, int W, int Cs, int Cout, int KH, int KW, int stride, int pad) {
-  if (!(g_conv_s2_patch && g_patch16 && g_conv_patch && g_conv_x3 && !g_lmkd_act_bf16) || Cs % 32 != 0 || stride != 2 || KH != 3 ||
+  if (!(g_conv_s2_patch && g_patch16 && g_conv_patch && conv_nprod(g_lmkd_act_bf16) >= 6) || Cs % 32 != 0 || stride != 2 || KH != 3 ||
       KW != 3 || pad != 1 || H % 2 != 0 || W % 2 != 0 || W / 2 + 1 > PATCH_HALO_MAX)
     return false;
   const int id = pick_conv_cfg((long)N * (H / 2) * (W / 2), 1, Cout, true);
   return id == 11 || id == 12;
 }
 
+// The stem (7x7 / stride 2 / pad 3 on the NHWC4 input, Cout <= 64) of the bf16-plane modes runs conv_stem_patch_kernel (conv_stem.h):
+// one workgroup per pair of output rows.  Returns the patch row pitch in pixels, or 0 when the launch is not of that kind.
 static int g_conv_stem_patch = 1;
 extern "C" int lmkd_conv_set_stem_patch(int on) { g_conv_stem_patch = on ? 1 : 0; return LMKD_OK; }
 static int stem_patch_pitch(int W, int Cs, int Cout, int KH, int KW, int stride, int pad) {
-  if (!g_conv_stem_patch || !(g_conv_x3 || g_conv_bf16) || Cs != 4 || KH != 7 || KW != 7 || stride != 2 || pad != 3 || Cout > 64) return 0;
+  if (!g_conv_stem_patch || !conv_planes() || Cs != 4 || KH != 7 || KW != 7 || stride != 2 || pad != 3 || Cout > 64) return 0;
   const int Wo = conv_out(W, KW, stride, pad);
   int wp = std::max(2 * Wo + 6, W + 3);
   wp += wp & 1;
   return (2 * Wo <= 256 && wp <= STEM_MAX_WP) ? wp : 0;
+}
+
+// ---- forward / data-gradient plan ------------------------------------------------------------------
+// Which kernel instance a forward or data-gradient launch runs, with its tile order, grid and LDS: decided once, by plan_fwd / plan_dgrad,
+// from the launch's arguments (shapes, frame segments, which operands are given), the switches and the arithmetic mode.  The launch
+// (launch_conv), the report (lmkd_conv2d_plan) and the buffer sizes (lmkd_conv2d_fwd_row_tiles_seg, lmkd_conv2d_bwd_data_bn_tiles_seg)
+// all read the same plan.
+enum class ConvFam : unsigned char {
+  Tile,       // fp32 MFMA tiles (conv_gemm_kernel), tile ids 1 - 6
+  Gather,     // bf16-plane im2col gather (conv_gemm_x3_kernel), ids 7 / 8 / 9
+  Patch,      // LDS-resident patch on the 32x32x16 MFMA (conv_patch_x3_kernel), ids 7 - 12; persistent in the two-plane form
+  Patch16,    // LDS-resident patch on the 16x16x32 MFMA (conv_patch16_x3_kernel), ids 11 / 12: SRC2 / BNB / EP / PRE forms
+  Patch1p,    // one-plane 256-row patch tiles (conv_patch_x3_kernel), ids 13 / 14
+  Stem,       // the stem's input-row patch (conv_stem_patch_kernel), reported as id 14
+};
+// loader / epilogue of the launch: plain, BatchNorm + ReLU in the loader (PRE), inference BatchNorm epilogue (EP), bf16 tensors in HBM,
+// the data gradient's BatchNorm-backward sums in the epilogue (BNB)
+enum ConvIO : unsigned char { IO_PLAIN, IO_PRE, IO_EP, IO_ACT16, IO_BNB };
+struct ConvPlan {
+  ConvFam fam;
+  unsigned char io;       // ConvIO
+  bool src2;              // Patch16: the stride-2 forward over the input's four parity classes
+  bool smallc;            // Tile / Gather: the padded stem input (Cs = 4)
+  bool bnb_form;          // data gradient: the launch has the fused BatchNorm-backward form (lmkd_conv2d_bwd_data_bn_tiles_seg)
+  bool amax_pass;         // max |y| (ConvGemmArgs::amax_out) needs a reduction pass behind the kernel: its epilogue does not fold it
+  int stats;              // Tile: conv_gemm_kernel STATS
+  int tile;               // lmkd_conv_set_tile id
+  int nprod;              // conv_nprod of the launch
+  int nclass, xcd;        // parity classes, XCD tile order (xcd_decode)
+  int halo;               // patch kernels: ConvGemmArgs::halo; Stem: the patch row pitch
+  int seg_m0, seg_t0, tiles_per_class, n_rt, n_ct;      // row tiles of the launch (conv_set_tiles): segment 0 has seg_t0 of each class's
+  int grid;               // workgroups; persistent launches: slots of the tile order (the grid then comes from the occupancy at launch)
+  int lds;                // dynamic LDS bytes
+};
+
+// geometry of a forward launch (no operands).  Taps are filled only where they fit (a report may ask for shapes no launch takes).
+static void fwd_geometry(ConvGemmArgs& a, int N, int H, int W, int Cs, int Cout, int KH, int KW, int stride, int pad, int seg_n0) {
+  memset(&a, 0, sizeof(a));
+  const int KWp = kw_padded(Cs, KW);
+  a.N = N; a.Hs = H; a.Ws = W; a.Cs = Cs;
+  a.Ho = conv_out(H, KH, stride, pad); a.Wo = conv_out(W, KW, stride, pad); a.Co = Cout;
+  a.Hr = a.Ho; a.Wr = a.Wo; a.rows_per_class = N * a.Ho * a.Wo; a.tiles_per_class = cdiv(a.rows_per_class, 128);
+  a.seg_m0 = seg_n0 * a.Ho * a.Wo;      // 0: one segment (conv_set_tiles)
+  a.sh = stride; a.omul = 1; a.nclass = 1;
+  a.Kp = KH * KWp * Cs;
+  a.div_hw = make_fastdiv(a.Hr * a.Wr); a.div_w = make_fastdiv(a.Wr);
+  if (Cs == 4) {
+    a.cps = 1;
+    if (KH > LMKD_MAX_TAPS) return;
+    a.ntap[0] = KH;
+    for (int kh = 0; kh < KH; ++kh) a.taps[0][kh] = Tap{kh - pad, -pad, kh * KWp * Cs};
+  } else {
+    a.cps = Cs / 32;
+    if (KH * KW > LMKD_MAX_TAPS) return;
+    a.ntap[0] = KH * KW;
+    for (int kh = 0; kh < KH; ++kh)
+      for (int kw = 0; kw < KW; ++kw) a.taps[0][kh * KW + kw] = Tap{kh - pad, kw - pad, (kh * KWp + kw) * Cs};
+  }
+}
+
+// geometry of a data-gradient launch dx[N,H,W,Cin] from dy[N,Ho,Wo,Cout] (no operands; taps only where they fit)
+static void dgrad_geometry(ConvGemmArgs& a, int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int seg_n0) {
+  memset(&a, 0, sizeof(a));
+  const int Ho = conv_out(H, KH, stride, pad), Wo = conv_out(W, KW, stride, pad);
+  a.N = N; a.Hs = Ho; a.Ws = Wo; a.Cs = Cout;
+  a.Ho = H; a.Wo = W; a.Co = Cin;
+  a.Kp = KH * KW * Cout; a.cps = Cout / 32;
+  a.sh = 1;
+  const bool fits = KH * KW <= LMKD_MAX_TAPS;
+  if (stride == 1) {
+    a.nclass = 1; a.omul = 1; a.Hr = H; a.Wr = W;
+    int nt = 0;
+    for (int kh = 0; kh < KH && fits; ++kh)
+      for (int kw = 0; kw < KW; ++kw) a.taps[0][nt++] = Tap{pad - kh, pad - kw, (kh * KW + kw) * Cout};
+    a.ntap[0] = nt;
+  } else {
+    // rows enumerated per input parity (ph,pw): ih = 2a+ph, source oh = (ih + pad - kh)/2 = a + (ph+pad-kh)/2
+    a.nclass = 4; a.omul = 2; a.Hr = (H + 1) / 2; a.Wr = (W + 1) / 2;
+    for (int c = 0; c < 4 && fits; ++c) {
+      const int ph = c >> 1, pw = c & 1;
+      int nt = 0;
+      for (int kh = 0; kh < KH; ++kh) {
+        if (((ph + pad - kh) & 1) != 0) continue;
+        for (int kw = 0; kw < KW; ++kw) {
+          if (((pw + pad - kw) & 1) != 0) continue;
+          // floor division (numerator may be negative)
+          const int nh = ph + pad - kh, nw = pw + pad - kw;
+          a.taps[c][nt++] = Tap{nh >= 0 ? nh / 2 : -((-nh) / 2), nw >= 0 ? nw / 2 : -((-nw) / 2), (kh * KW + kw) * Cout};
+        }
+      }
+      a.ntap[c] = nt;
+    }
+  }
+  a.rows_per_class = N * a.Hr * a.Wr;
+  a.seg_m0 = seg_n0 * a.Hr * a.Wr;
+  a.tiles_per_class = cdiv(a.rows_per_class, 128);
+  a.div_hw = make_fastdiv(a.Hr * a.Wr); a.div_w = make_fastdiv(a.Wr);
+}
+
+// The kernel choice of every forward / data-gradient launch but the stem's.  halo: patch_halo of the launch (-1: not a patch launch);
+// same: same-size convolution (the tile may be one only the patch kernel has); src2: the stride-2 forward's parity-class form.
+static ConvPlan plan_conv(const ConvGemmArgs& a, int halo, bool same, bool smallc, int stats, bool src2) {
+  ConvPlan p;
+  memset(&p, 0, sizeof(p));
+  const bool act16 = g_lmkd_act_bf16;
+  const int ncols = a.Co;
+  p.io = a.ep_stats ? IO_EP : act16 ? IO_ACT16 : a.pre_stats ? IO_PRE : a.bnb_x ? IO_BNB : IO_PLAIN;
+  p.src2 = src2; p.smallc = smallc; p.stats = stats; p.nclass = a.nclass; p.halo = halo;
+  int id = pick_conv_cfg(a.rows_per_class, a.nclass, ncols, same);
+  // (the inference epilogue of the padded stem input exists on the fp32 tiles only)
+  if (conv_planes() && !(stats == 2 && smallc)) {
+    if (halo < 0) {      // the gather kernel: the same tile height (the BatchNorm partials' row count) where the patch kernel's tile was picked
+      id = id == 10 || id == 13 || id == 14 ? 7 : (id == 11 ? 9 : (id == 12 ? 8 : id));
+      p.fam = ConvFam::Gather;
+      p.nprod = conv_nprod(act16);
+    } else if (id == 13 || id == 14) {
+      p.fam = ConvFam::Patch1p;
+      p.nprod = 1;
+    } else {
+      const bool h2 = conv_nprod(act16, a.h2_xw && !a.ep_stats) == 3;      // two fp16 planes (not the inference epilogue)
+      const bool h2_on_32 = g_patch16 == 1 && id == 11 && ncols <= 64 && h2 && !src2;
+      const bool p16 = (id == 11 || id == 12) && g_patch16 && conv_nprod(act16) >= 6;
+      // the fused BatchNorm-backward sums: conv_patch16_x3_kernel's one-class launches (BNB), or the two-plane form on 32x32x16
+      // (h2_on_32), whose epilogue takes them as well
+      p.bnb_form = p16 && a.nclass == 1 && ncols % 4 == 0;
+      if (p16 && !h2_on_32) {
+        p.fam = ConvFam::Patch16;
+        p.nprod = conv_nprod(false, a.h2_xw);      // (the inference epilogue too)
+      } else {
+        p.fam = ConvFam::Patch;
+        p.nprod = h2 ? 3 : conv_nprod(act16);
+      }
+    }
+  } else {
+    p.fam = ConvFam::Tile;
+    if (id != 1 && id != 2 && id != 3 && id != 5 && id != 6) id = 4;
+  }
+  p.tile = id;
+  // row tiles, per frame segment (conv_set_tiles)
+  const int bm = cfg_bm(id);
+  p.seg_m0 = (a.seg_m0 <= 0 || a.seg_m0 >= a.rows_per_class) ? a.rows_per_class : a.seg_m0;
+  p.seg_t0 = cdiv(p.seg_m0, bm);
+  p.tiles_per_class = p.seg_t0 + cdiv(a.rows_per_class - p.seg_m0, bm);
+  p.n_rt = a.nclass * p.tiles_per_class;
+  p.n_ct = cdiv(ncols, cfg_bn(id));
+  p.xcd = g_xcd_mode != 0 && p.n_ct >= 8 && (p.n_ct & 7) == 0;
+  p.grid = xcd_grid(p.n_rt, p.n_ct, p.xcd);
+  if (p.fam == ConvFam::Patch || p.fam == ConvFam::Patch16 || p.fam == ConvFam::Patch1p)
+    p.lds = (int)patch_lds_bytes(bm, halo, p.nprod == 1 ? 1 : (p.nprod == 3 && p.fam == ConvFam::Patch ? 2 : 3));
+  // (x3_epilogue<.., H2> and conv_patch16_x3_kernel fold max |y| themselves)
+  p.amax_pass = !act16 && p.fam != ConvFam::Patch16 && !(p.fam == ConvFam::Patch && p.nprod == 3);
+  return p;
+}
+
+// a: fwd_geometry (+ the operands; only whether they are given is read)
+static ConvPlan plan_fwd(const ConvGemmArgs& a, int KH, int KW, int pad) {
+  const int N = a.N, H = a.Hs, W = a.Ws, Cs = a.Cs, Cout = a.Co, stride = a.sh;
+  if (const int wp = a.ep_stats ? 0 : stem_patch_pitch(W, Cs, Cout, KH, KW, stride, pad)) {      // one workgroup per output row pair
+    ConvPlan p;
+    memset(&p, 0, sizeof(p));
+    p.fam = ConvFam::Stem;
+    p.io = g_lmkd_act_bf16 ? IO_ACT16 : IO_PLAIN;
+    p.tile = 14; p.nclass = 1; p.halo = wp;
+    p.nprod = conv_nprod(g_lmkd_act_bf16, a.h2_xw);
+    const int seg_n0 = a.seg_m0 > 0 && a.seg_m0 < a.rows_per_class ? a.seg_m0 / (a.Ho * a.Wo) : N;
+    p.seg_t0 = seg_n0 * cdiv(a.Ho, 2);
+    p.n_rt = p.tiles_per_class = p.grid = N * cdiv(a.Ho, 2);
+    p.n_ct = 1;
+    p.lds = (p.nprod == 1 ? 1 : 3) * 9 * wp * 8;
+    return p;      // (no max |y| pass behind the stem)
+  }
+  const int stats = a.ep_stats ? 2 : (a.stat_partial ? 1 : 0);
+  // stride-2 3x3 forward on the patch kernel (SRC2): even input, the 16x16x32 instances (tile ids 11 / 12), no BatchNorm loader.  Its
+  // taps lie within -1 .. 0 of the class grid (= the output grid): halo Wo + 1
+  if (!a.pre_stats && fwd_s2_patch_ok(N, H, W, Cs, Cout, KH, KW, stride, pad)) return plan_conv(a, a.Wo + 1, true, false, stats, true);
+  const int halo = Cs == 4 || !a.ntap[0] ? -1 : patch_halo(a);
+  return plan_conv(a, halo, conv_same_size(H, W, KH, KW, stride, pad), Cs == 4, stats, false);
+}
+
+// a: dgrad_geometry (+ the operands)
+static ConvPlan plan_dgrad(const ConvGemmArgs& a) {
+  const int halo = a.ntap[0] ? patch_halo(a) : -1;
+  return plan_conv(a, halo, halo >= 0, false, 0, false);
+}
+
+// The stride-2 forward's parity-class form of the arguments (ConvGemmArgs::src2)
+static void fwd_src2_args(ConvGemmArgs& a, int W, int KWp) {
+  const int Cs = a.Cs;
+  a.src2 = 1; a.s2_ncls = 4; a.s2_wfull = W;
+  a.Hs = a.Ho; a.Ws = a.Wo; a.sh = 1;
+  static const int order[4][2] = {{1, 1}, {1, 0}, {0, 1}, {0, 0}};      // classes by tap count 4, 2, 2, 1
+  int nt = 0;
+  for (int c = 0; c < 4; ++c) {
+    const int sph = order[c][0], spw = order[c][1];
+    a.s2_t0[c] = nt;
+    a.s2_off[c] = (sph * W + spw) * Cs;
+    for (int kh = 0; kh < 3; ++kh) {
+      if (((kh - 1) & 1) != sph) continue;
+      for (int kw = 0; kw < 3; ++kw) {
+        if (((kw - 1) & 1) != spw) continue;
+        a.taps[0][nt++] = Tap{(kh - 1 - sph) / 2, (kw - 1 - spw) / 2, (kh * KWp + kw) * Cs};
+      }
+    }
+  }
+  a.s2_t0[4] = nt;
+  a.ntap[0] = nt;
+}
+
+// ---- launching a plan ------------------------------------------------------------------------------
+// f(std::integral_constant<int, P>{}) for the plan's product count n, P one of the counts the call site lists: a site instantiates
+// exactly the instances it names.  Every two-plane launch passes through here (lmkd_conv_h2_launches).
+template <int... Ps, class F>
+static inline void with_nprod(int n, F&& f) {
+  if (n == 3) ++g_h2_launches;
+  (void)((n == Ps ? (f(std::integral_constant<int, Ps>{}), true) : false) || ...);
+}
+
+template <class Cfg, int NPROD, bool PRE, int IO>
+static void launch_patch_instance(ConvGemmArgs& a, const ConvPlan& p, hipStream_t s) {
+  constexpr auto K = conv_patch_x3_kernel<Cfg, NPROD, PRE, IO>;
+  lds_attr_once<K>((int)patch_lds_bytes(Cfg::BM, PATCH_HALO_MAX, NPROD == 1 ? 1 : 3));
+  a.grid_total = p.grid;      // (one-plane / three-plane instances: one workgroup per tile, conv_patch.h PERSIST)
+  a.grid_step = NPROD == 3 ? persistent_grid<K>(Cfg::THREADS, p.lds, p.grid) : p.grid;
+  hipLaunchKernelGGL((conv_patch_x3_kernel<Cfg, NPROD, PRE, IO>), dim3(a.grid_step), dim3(Cfg::THREADS), p.lds, s, a);
+}
+// conv_patch_x3_kernel (Patch, Patch1p)
+template <class Cfg, bool ONE_PLANE = false>
+static void launch_patch(ConvGemmArgs& a, const ConvPlan& p, hipStream_t s) {
+  if constexpr (ONE_PLANE) {
+    if (p.io == IO_EP) launch_patch_instance<Cfg, 1, false, 4>(a, p, s);
+    else if (p.io == IO_ACT16) launch_patch_instance<Cfg, 1, false, 3>(a, p, s);
+    else if (p.io == IO_PRE) launch_patch_instance<Cfg, 1, true, 0>(a, p, s);
+    else launch_patch_instance<Cfg, 1, false, 0>(a, p, s);
+  } else {
+    if (p.io == IO_EP) with_nprod<1, 6, 9>(p.nprod, [&](auto np) { launch_patch_instance<Cfg, np, false, 4>(a, p, s); });
+    else if (p.io == IO_ACT16) launch_patch_instance<Cfg, 1, false, 3>(a, p, s);
+    else if (p.io == IO_PRE) with_nprod<1, 3, 6, 9>(p.nprod, [&](auto np) { launch_patch_instance<Cfg, np, true, 0>(a, p, s); });
+    else with_nprod<1, 3, 6, 9>(p.nprod, [&](auto np) { launch_patch_instance<Cfg, np, false, 0>(a, p, s); });
+  }
+}
+template <class Cfg, int NPROD, bool PRE, bool EP, bool SRC2 = false, bool BNB = false>
+static void launch_patch16_instance(const ConvGemmArgs& a, const ConvPlan& p, hipStream_t s) {
+  lds_attr_once<conv_patch16_x3_kernel<Cfg, NPROD, PRE, EP, SRC2, BNB>>((int)patch_lds_bytes(Cfg::BM, PATCH_HALO_MAX, 3));
+  hipLaunchKernelGGL((conv_patch16_x3_kernel<Cfg, NPROD, PRE, EP, SRC2, BNB>), dim3(p.grid), dim3(Cfg::THREADS), p.lds, s, a);
+}
+// conv_patch16_x3_kernel (Patch16; the benchmark's tiles 11 / 12)
+template <class Cfg>
+static void launch_patch16(const ConvGemmArgs& a, const ConvPlan& p, hipStream_t s) {
+  with_nprod<3, 6, 9>(p.nprod, [&](auto np) {
+    if (p.src2 && p.io == IO_EP) launch_patch16_instance<Cfg, np, false, true, true>(a, p, s);      // inference, stride 2
+    else if (p.src2) launch_patch16_instance<Cfg, np, false, false, true>(a, p, s);
+    else if (p.io == IO_EP) launch_patch16_instance<Cfg, np, false, true>(a, p, s);      // BatchNorm affine (+ residual, ReLU)
+    else if (p.io == IO_PRE) launch_patch16_instance<Cfg, np, true, false>(a, p, s);
+    else if (p.io == IO_BNB) launch_patch16_instance<Cfg, np, false, false, false, true>(a, p, s);
+    else launch_patch16_instance<Cfg, np, false, false>(a, p, s);
+  });
+}
+// conv_gemm_x3_kernel (Gather).  ONE instance serves launches with and without BatchNorm partials (stat_partial null -> nothing written):
+// hipcc schedules the main loop of the instance without the statistics epilogue worse (register copies in front of the MFMAs: 105 vs
+// 148 TFLOP/s on the same layer), so that instance is not built
+template <class Cfg, bool SMALLC>
+static void launch_gather(const ConvGemmArgs& a, const ConvPlan& p, hipStream_t s) {
+  const dim3 grid(p.grid), block(Cfg::THREADS);
+  if (p.io == IO_ACT16) {      // bf16 tensors in HBM (one-plane mode): the loader copies, the epilogue rounds; the stem input stays fp32
+    if constexpr (SMALLC) hipLaunchKernelGGL((conv_gemm_x3_kernel<Cfg, true, true, 1, false, 2>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((conv_gemm_x3_kernel<Cfg, false, true, 1, false, 3>), grid, block, 0, s, a);
+    return;
+  }
+  if constexpr (!SMALLC) {
+    if (p.io == IO_EP) {      // inference epilogue (x3_epilogue EP): stride-2 / 1x1-downsample convolutions of an eval forward
+      with_nprod<1, 6, 9>(p.nprod, [&](auto np) { hipLaunchKernelGGL((conv_gemm_x3_kernel<Cfg, false, true, np, false, 4>), grid, block, 0, s, a); });
+      return;
+    }
+    if (p.io == IO_PRE) {      // training forward fed by relu(BatchNorm(raw)): normalise + rectify when the tile is stored to LDS
+      with_nprod<1, 6, 9>(p.nprod, [&](auto np) { hipLaunchKernelGGL((conv_gemm_x3_kernel<Cfg, false, true, np, true>), grid, block, 0, s, a); });
+      return;
+    }
+  }
+  with_nprod<1, 6, 9>(p.nprod, [&](auto np) { hipLaunchKernelGGL((conv_gemm_x3_kernel<Cfg, SMALLC, true, np>), grid, block, 0, s, a); });
+}
+// conv_gemm_kernel (Tile)
+template <class Cfg>
+static void launch_tile(const ConvGemmArgs& a, const ConvPlan& p, hipStream_t s) {
+  const dim3 grid(p.grid), block(Cfg::THREADS);
+  if (p.smallc) {
+    if (p.stats == 2) hipLaunchKernelGGL((conv_gemm_kernel<Cfg, true, 2, false>), grid, block, 0, s, a);
+    else if (p.stats == 1) hipLaunchKernelGGL((conv_gemm_kernel<Cfg, true, 1, false>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((conv_gemm_kernel<Cfg, true, 0, false>), grid, block, 0, s, a);
+  } else if (p.stats == 2) hipLaunchKernelGGL((conv_gemm_kernel<Cfg, false, 2, false>), grid, block, 0, s, a);
+  else if (p.stats == 1 && p.io == IO_PRE)      // the training forward of a conv that follows a BatchNorm + ReLU
+    hipLaunchKernelGGL((conv_gemm_kernel<Cfg, false, 1, false, true>), grid, block, 0, s, a);
+  else if (p.stats == 1) hipLaunchKernelGGL((conv_gemm_kernel<Cfg, false, 1, false>), grid, block, 0, s, a);
+  else hipLaunchKernelGGL((conv_gemm_kernel<Cfg, false, 0, false>), grid, block, 0, s, a);
+}
+
+// (round 4: conv_patch16_x3_kernel on 256 x 64 tiles - four waves stacked over the rows, wave tiles 64 x 64, two workgroups per CU - was
+// built as tile id 15 and measured SLOWER than id 11 on every layer, 443 vs 383 us on layer 1 in fp32h2: profiles/r04_tile_ab.txt; removed)
+static int launch_conv(ConvGemmArgs& a, const ConvPlan& p, hipStream_t s) {
+  if (p.fam == ConvFam::Stem) {
+    a.halo = p.halo;      // row pitch of the input-row patch
+    a.n_rt = p.n_rt; a.n_ct = 1;
+    const dim3 grid(p.grid), block(512);
+    // two output rows per workgroup (one row, four waves: 557 vs 447 us at 200 frames)
+    if (p.io == IO_ACT16) hipLaunchKernelGGL((conv_stem_patch_kernel<1, true, 2>), grid, block, p.lds, s, a);
+    else with_nprod<1, 3, 6, 9>(p.nprod, [&](auto np) { hipLaunchKernelGGL((conv_stem_patch_kernel<np, false, 2>), grid, block, p.lds, s, a); });
+    LMKD_CHECK_LAUNCH("conv_stem_patch_kernel");
+    return LMKD_OK;
+  }
+  a.seg_m0 = p.seg_m0; a.seg_t0 = p.seg_t0; a.tiles_per_class = p.tiles_per_class;
+  a.n_rt = p.n_rt; a.n_ct = p.n_ct; a.xcd_mode = p.xcd;
+  switch (p.fam) {
+    case ConvFam::Tile:
+      switch (p.tile) {
+        case 1: launch_tile<TileCfg<128, 128, 2, 2>>(a, p, s); break;
+        case 2: launch_tile<TileCfg<128, 64, 2, 2>>(a, p, s); break;
+        case 3: launch_tile<TileCfg<64, 64, 2, 2>>(a, p, s); break;
+        case 5: launch_tile<TileCfg<128, 128, 2, 4>>(a, p, s); break;
+        case 6: launch_tile<TileCfg<128, 64, 4, 2>>(a, p, s); break;
+        default: launch_tile<TileCfg<64, 128, 2, 2>>(a, p, s); break;
+      }
+      LMKD_CHECK_LAUNCH("conv_gemm_kernel");
+      return LMKD_OK;
+    case ConvFam::Gather:
+      switch (p.tile * 2 + p.smallc) {
+        case 14: launch_gather<X3Cfg<256, 64, 4, 2>, false>(a, p, s); break;
+        case 15: launch_gather<X3Cfg<256, 64, 4, 2>, true>(a, p, s); break;
+        case 16: launch_gather<X3Cfg<128, 128, 2, 4>, false>(a, p, s); break;
+        case 17: launch_gather<X3Cfg<128, 128, 2, 4>, true>(a, p, s); break;
+        case 19: launch_gather<X3Cfg<128, 64, 4, 2>, true>(a, p, s); break;
+        default: launch_gather<X3Cfg<128, 64, 4, 2>, false>(a, p, s); break;
+      }
+      LMKD_CHECK_LAUNCH("conv_gemm_x3_kernel");
+      return LMKD_OK;
+    default: break;
+  }
+  a.taps_pm1 = taps_within_one(a);
+  a.halo = p.halo;
+  switch (p.tile) {
+    case 7: launch_patch<X3Cfg<256, 64, 4, 2>>(a, p, s); break;
+    case 8: launch_patch<X3Cfg<128, 128, 2, 4>>(a, p, s); break;
+    case 10: launch_patch<X3Cfg<256, 128, 2, 4>>(a, p, s); break;
+    case 11:
+      if (p.fam == ConvFam::Patch16) launch_patch16<X3Cfg<128, 64, 2, 2, 3>>(a, p, s);
+      else launch_patch<X3Cfg<128, 64, 2, 2, 3>>(a, p, s);
+      break;
+    case 12:
+      if (p.fam == ConvFam::Patch16) launch_patch16<X3Cfg<128, 128, 2, 2, 2>>(a, p, s);
+      else launch_patch<X3Cfg<128, 128, 2, 2, 2>>(a, p, s);
+      break;
+    case 13: launch_patch<X3Cfg<256, 128, 2, 2, 2>, true>(a, p, s); break;      // (one-plane modes only: 256-row tiles with four waves)
+    case 14: launch_patch<X3Cfg<256, 64, 2, 2, 2>, true>(a, p, s); break;
+    default: launch_patch<X3Cfg<128, 64, 4, 2>>(a, p, s); break;
+  }
+  LMKD_CHECK_LAUNCH("conv_patch_x3_kernel");
+  return LMKD_OK;
 }
 
 // number of row tiles (= rows of the BN partial-statistics buffer) of a forward conv
@@ -1291,16 +1428,12 @@ extern "C" int lmkd_conv2d_fwd_row_tiles_cs(int N, int H, int W, int Cs, int Cou
 // two frame segments in one launch (ConvGemmArgs::seg_m0): frames [0, seg_n0) | [seg_n0, N).  Returns the rows of the partial-sum
 // buffer; *tiles0 (host pointer, nullable) receives how many of them - the leading ones - belong to segment 0.  seg_n0 = 0 or N: one segment.
 extern "C" int lmkd_conv2d_fwd_row_tiles_seg(int N, int H, int W, int Cs, int Cout, int KH, int KW, int stride, int pad, int seg_n0, int* tiles0) {
-  if (seg_n0 <= 0 || seg_n0 >= N) seg_n0 = N;
-  const int Ho = conv_out(H, KH, stride, pad), Wo = conv_out(W, KW, stride, pad);
-  if (stem_patch_pitch(W, Cs, Cout, KH, KW, stride, pad)) {
-    if (tiles0) *tiles0 = seg_n0 * cdiv(Ho, 2);
-    return N * cdiv(Ho, 2);
-  }
-  const long M = (long)N * Ho * Wo, M0 = (long)seg_n0 * Ho * Wo;
-  const int bm = cfg_bm(pick_conv_cfg(M, 1, Cout, conv_same_size(H, W, KH, KW, stride, pad)));
-  if (tiles0) *tiles0 = cdiv(M0, bm);
-  return cdiv(M0, bm) + cdiv(M - M0, bm);
+  if (seg_n0 <= 0 || seg_n0 >= N) seg_n0 = 0;
+  ConvGemmArgs a;
+  fwd_geometry(a, N, H, W, Cs, Cout, KH, KW, stride, pad, seg_n0);
+  const ConvPlan p = plan_fwd(a, KH, KW, pad);
+  if (tiles0) *tiles0 = p.seg_t0;
+  return p.tiles_per_class;
 }
 extern "C" int lmkd_conv2d_fwd_row_tiles(int N, int H, int W, int Cout, int KH, int KW, int stride, int pad) {
   return lmkd_conv2d_fwd_row_tiles_cs(N, H, W, 32, Cout, KH, KW, stride, pad);
@@ -1311,7 +1444,7 @@ static int conv2d_fwd_impl(const float* x, const float* wp, float* y, float* sta
                            int pad, void* stream, const float* pre_stats = nullptr, int seg_n0 = 0, const lmkd_amax_desc* am = nullptr) {
   LMKD_REQUIRE(x && wp && y, "lmkd_conv2d_fwd: null pointer");
   if (seg_n0 <= 0 || seg_n0 >= N) seg_n0 = 0;
-  LMKD_REQUIRE(!seg_n0 || ((g_conv_x3 || g_conv_bf16) && !ep_stats), "lmkd_conv2d_fwd_seg: two frame segments exist in the bf16-plane modes (training / plain forward)");
+  LMKD_REQUIRE(!seg_n0 || (conv_planes() && !ep_stats), "lmkd_conv2d_fwd_seg: two frame segments exist in the bf16-plane modes (training / plain forward)");
   LMKD_REQUIRE(aligned16(x) && aligned16(wp), "lmkd_conv2d_fwd: x / packed weights must be 16-byte aligned");
   LMKD_REQUIRE(Cs % 32 == 0 || Cs == 4, "lmkd_conv2d_fwd: channel count %d must be 4 (padded stem) or a multiple of 32", Cs);
   LMKD_REQUIRE(N > 0 && H > 0 && W > 0 && Cout > 0, "lmkd_conv2d_fwd: empty tensor");
@@ -1320,96 +1453,35 @@ static int conv2d_fwd_impl(const float* x, const float* wp, float* y, float* sta
   LMKD_REQUIRE(!smallc || KWp == 8, "lmkd_conv2d_fwd: padded-stem path needs KW <= 8");
   LMKD_REQUIRE(KH * (smallc ? 1 : KW) <= LMKD_MAX_TAPS, "lmkd_conv2d_fwd: kernel %dx%d has too many taps", KH, KW);
   LMKD_REQUIRE(H < 32768 && W < 32768, "lmkd_conv2d_fwd: spatial dims too large");
+  const bool act16 = g_lmkd_act_bf16;
+  LMKD_REQUIRE(!pre_stats || (stat_partial && !smallc && !act16),
+               "lmkd_conv2d_fwd_pre: the fused BatchNorm+ReLU loader exists for the training forward with fp32 activations (stat_partial given, Cs %% 32 == 0)");
+  LMKD_REQUIRE(!act16 || (conv_nprod() == 1 && !ep_stats), "bf16 activations need lmkd_conv_set_compute_dtype(1) (training / plain forward)");
+  const int Ho = conv_out(H, KH, stride, pad), Wo = conv_out(W, KW, stride, pad);
+  LMKD_REQUIRE(Ho > 0 && Wo > 0, "lmkd_conv2d_fwd: empty output");
+  LMKD_REQUIRE((long)N * H * W * Cs < 2147483647L && (long)N * Ho * Wo * Cout < 2147483647L,
+               "lmkd_conv2d_fwd: tensor exceeds 2^31 elements");
+  // the bf16-plane kernels (patch / stem / gather) address the gathered tensor with 32-bit BYTE offsets through a buffer resource
+  LMKD_REQUIRE(!conv_planes() || (long)N * H * W * Cs * (act16 && Cs != 4 ? 2 : 4) < 0xffffffe0L,
+               "lmkd_conv2d_fwd: input tensor exceeds the 4 GiB buffer range of the bf16-plane kernels");
   ConvGemmArgs a;
-  memset(&a, 0, sizeof(a));
+  fwd_geometry(a, N, H, W, Cs, Cout, KH, KW, stride, pad, seg_n0);
   a.src = x; a.wpk = wp; a.out = y; a.stat_partial = stat_partial;
   a.h2_xw = am ? (const unsigned*)am->x_words : nullptr;
   a.amax_out = am ? (unsigned*)am->out_words : nullptr;
   note_fenced(am);
   a.ep_stats = ep_stats; a.ep_res = ep_res; a.ep_relu = ep_relu;
   a.pre_stats = pre_stats;
-  LMKD_REQUIRE(!pre_stats || (stat_partial && !smallc && !g_lmkd_act_bf16),
-               "lmkd_conv2d_fwd_pre: the fused BatchNorm+ReLU loader exists for the training forward with fp32 activations (stat_partial given, Cs %% 32 == 0)");
-  LMKD_REQUIRE(!g_lmkd_act_bf16 || (g_conv_bf16 && !ep_stats), "bf16 activations need lmkd_conv_set_compute_dtype(1) (training / plain forward)");
-  a.N = N; a.Hs = H; a.Ws = W; a.Cs = Cs;
-  a.Ho = conv_out(H, KH, stride, pad); a.Wo = conv_out(W, KW, stride, pad); a.Co = Cout;
-  LMKD_REQUIRE(a.Ho > 0 && a.Wo > 0, "lmkd_conv2d_fwd: empty output");
-  LMKD_REQUIRE((long)N * H * W * Cs < 2147483647L && (long)N * a.Ho * a.Wo * Cout < 2147483647L,
-               "lmkd_conv2d_fwd: tensor exceeds 2^31 elements");
-  // the bf16-plane kernels (patch / stem / gather) address the gathered tensor with 32-bit BYTE offsets through a buffer resource
-  LMKD_REQUIRE(!(g_conv_x3 || g_conv_bf16) || (long)N * H * W * Cs * (g_lmkd_act_bf16 && Cs != 4 ? 2 : 4) < 0xffffffe0L,
-               "lmkd_conv2d_fwd: input tensor exceeds the 4 GiB buffer range of the bf16-plane kernels");
-  a.Hr = a.Ho; a.Wr = a.Wo; a.rows_per_class = N * a.Ho * a.Wo; a.tiles_per_class = cdiv(a.rows_per_class, 128);
-  a.seg_m0 = seg_n0 * a.Ho * a.Wo;      // 0: one segment (conv_set_tiles)
-  a.sh = stride; a.omul = 1; a.nclass = 1;
-  a.same = conv_same_size(H, W, KH, KW, stride, pad) ? 1 : 0;      // as in lmkd_conv2d_fwd_row_tiles
-  a.Kp = KH * KWp * Cs;
-  a.div_hw = make_fastdiv(a.Hr * a.Wr); a.div_w = make_fastdiv(a.Wr);
-  if (smallc) {
-    a.cps = 1;
-    a.ntap[0] = KH;
-    for (int kh = 0; kh < KH; ++kh) a.taps[0][kh] = Tap{kh - pad, -pad, kh * KWp * Cs};
-  } else {
-    a.cps = Cs / 32;
-    a.ntap[0] = KH * KW;
-    for (int kh = 0; kh < KH; ++kh)
-      for (int kw = 0; kw < KW; ++kw) a.taps[0][kh * KW + kw] = Tap{kh - pad, kw - pad, (kh * KWp + kw) * Cs};
+  const ConvPlan p = plan_fwd(a, KH, KW, pad);
+  if (p.src2) {
+    LMKD_REQUIRE((long)N * H * W * Cs * 4 < 2147483647L, "lmkd_conv2d_fwd: input tensor exceeds the 2 GiB offset range of the stride-2 patch form");
+    fwd_src2_args(a, W, KWp);
   }
-  hipStream_t s = (hipStream_t)stream;
-  // stride-2 3x3 forward on the patch kernel (SRC2): even input, the 16x16x32 instances (tile ids 11 / 12), no BatchNorm loader
-  if (!pre_stats && fwd_s2_patch_ok(N, H, W, Cs, Cout, KH, KW, stride, pad)) {
-    {
-      a.src2 = 1; a.s2_ncls = 4; a.s2_wfull = W;
-      a.Hs = a.Ho; a.Ws = a.Wo; a.sh = 1; a.same = 1;
-      LMKD_REQUIRE((long)N * H * W * Cs * 4 < 2147483647L, "lmkd_conv2d_fwd: input tensor exceeds the 2 GiB offset range of the stride-2 patch form");
-      static const int order[4][2] = {{1, 1}, {1, 0}, {0, 1}, {0, 0}};      // classes by tap count 4, 2, 2, 1
-      int nt = 0;
-      for (int c = 0; c < 4; ++c) {
-        const int sph = order[c][0], spw = order[c][1];
-        a.s2_t0[c] = nt;
-        a.s2_off[c] = (sph * W + spw) * Cs;
-        for (int kh = 0; kh < 3; ++kh) {
-          if (((kh - 1) & 1) != sph) continue;
-          for (int kw = 0; kw < 3; ++kw) {
-            if (((kw - 1) & 1) != spw) continue;
-            a.taps[0][nt++] = Tap{(kh - 1 - sph) / 2, (kw - 1 - spw) / 2, (kh * KWp + kw) * Cs};
-          }
-        }
-      }
-      a.s2_t0[4] = nt;
-      a.ntap[0] = nt;
-    }
-  }
-  if (const int wp = ep_stats ? 0 : stem_patch_pitch(W, Cs, Cout, KH, KW, stride, pad)) {
-    a.halo = wp;      // row pitch of the input-row patch
-    a.n_rt = N * cdiv(a.Ho, 2); a.n_ct = 1;
-    const int npl = (g_conv_bf16 || g_lmkd_act_bf16) ? 1 : 3;
-    const size_t lds = (size_t)npl * 9 * wp * 8;
-    const dim3 grid(a.n_rt), block(512);
-#define LMKD_STEM(OR)                                                                                                  \
-  do {                                                                                                                 \
-    if (g_lmkd_act_bf16) hipLaunchKernelGGL((conv_stem_patch_kernel<1, true, OR>), grid, block, lds, s, a);            \
-    else if (g_conv_bf16) hipLaunchKernelGGL((conv_stem_patch_kernel<1, false, OR>), grid, block, lds, s, a);          \
-    else if (g_conv_x3 == 9) hipLaunchKernelGGL((conv_stem_patch_kernel<9, false, OR>), grid, block, lds, s, a);       \
-    else if (g_conv_h2 && a.h2_xw) {                                                                                   \
-      hipLaunchKernelGGL((conv_stem_patch_kernel<3, false, OR>), grid, block, lds, s, a);                              \
-      ++g_h2_launches;                                                                                                 \
-    } else hipLaunchKernelGGL((conv_stem_patch_kernel<6, false, OR>), grid, block, lds, s, a);                         \
-  } while (0)
-    LMKD_STEM(2);      // two output rows per workgroup (one row, four waves: 557 vs 447 us at 200 frames)
-#undef LMKD_STEM
-    LMKD_CHECK_LAUNCH("conv_stem_patch_kernel");
-    return LMKD_OK;
-  }
-  t_amax_recorded = false;
-  int rc;
-  if (ep_stats) rc = smallc ? launch_conv_gemm<true, 2>(a, Cout, s) : launch_conv_gemm<false, 2>(a, Cout, s);
-  else if (smallc) rc = stat_partial ? launch_conv_gemm<true, 1>(a, Cout, s) : launch_conv_gemm<true, 0>(a, Cout, s);
-  else rc = stat_partial ? launch_conv_gemm<false, 1>(a, Cout, s) : launch_conv_gemm<false, 0>(a, Cout, s);
-  if (rc == LMKD_OK && a.amax_out && !t_amax_recorded && !g_lmkd_act_bf16) {
+  int rc = launch_conv(a, p, (hipStream_t)stream);
+  if (rc == LMKD_OK && a.amax_out && p.amax_pass) {
     // lmkd_conv_output_amax on a launch whose kernel does not fold the maximum in its epilogue: a reduction pass of its own per frame
     // segment (rare shapes; the trunk's 3x3 convolutions all run conv_patch16_x3_kernel) - the words are never left at "unknown"
-    const long per = (long)a.Ho * a.Wo * Cout, n0 = seg_n0 ? seg_n0 * per : (long)N * per;
+    const long per = (long)Ho * Wo * Cout, n0 = seg_n0 ? seg_n0 * per : (long)N * per;
     rc = amax_impl(y, n0, a.amax_out, 1, stream, false);
     if (rc == LMKD_OK && seg_n0) rc = amax_impl(y + n0, (long)N * per - n0, a.amax_out + LMKD_AMAX_SEG_WORDS, 1, stream, false);
   }
@@ -1421,7 +1493,7 @@ extern "C" int lmkd_conv2d_fwd(const float* x, const float* wp, float* y, float*
   return conv2d_fwd_impl(x, wp, y, stat_partial, nullptr, nullptr, 0, N, H, W, Cs, Cout, KH, KW, stride, pad, stream);
 }
 
-// Training form for a convolution that consumes relu(BatchNorm(x_raw)): x_raw is the previous convolution's raw output and
+// Training form for a convolution that consumes relu(BatchNorm(x)): x_raw is the previous convolution's raw output and
 // pre_stats its [5][Cs] BatchNorm table (lmkd_bn_finalize); normalise + ReLU happen in the loader, bit-identical to running
 // lmkd_bn_apply first (torchvision BasicBlock: conv2(relu(bn1(conv1(x)))), resnet18_2fc.py:41-42).
 // lmkd_conv2d_fwd / lmkd_conv2d_fwd_pre (pre_stats nullable) over TWO frame segments [0, seg_n0) | [seg_n0, N) of one tensor - the support-
@@ -1445,7 +1517,7 @@ extern "C" int lmkd_conv2d_fwd_bn(const float* x, const float* wp, float* y, con
                                   int N, int H, int W, int Cs, int Cout, int KH, int KW, int stride, int pad, void* stream, const lmkd_amax_desc* amax) {
   LMKD_REQUIRE(bn_stats, "lmkd_conv2d_fwd_bn: BatchNorm table missing");
   LMKD_REQUIRE(!g_lmkd_act_bf16, "lmkd_conv2d_fwd_bn: fp32 tensors only (with bf16 tensors run lmkd_conv2d_fwd + lmkd_bn_apply)");
-  LMKD_REQUIRE(!(g_conv_x3 || g_conv_bf16) || Cs % 32 == 0, "lmkd_conv2d_fwd_bn: the bf16-plane modes need Cs %% 32 == 0 (Cs=%d)", Cs);
+  LMKD_REQUIRE(!conv_planes() || Cs % 32 == 0, "lmkd_conv2d_fwd_bn: the bf16-plane modes need Cs %% 32 == 0 (Cs=%d)", Cs);
   return conv2d_fwd_impl(x, wp, y, nullptr, bn_stats, res, relu, N, H, W, Cs, Cout, KH, KW, stride, pad, stream, nullptr, 0, amax);
 }
 
@@ -1453,52 +1525,19 @@ extern "C" int lmkd_conv2d_fwd_bn(const float* x, const float* wp, float* y, con
 static int bwd_data_args(ConvGemmArgs& a, const float* dy, const float* wd, float* dx, int N, int H, int W, int Cin, int Cout, int KH, int KW,
                          int stride, int pad, int accumulate, int seg_n0 = 0, const lmkd_amax_desc* am = nullptr) {
   if (seg_n0 <= 0 || seg_n0 >= N) seg_n0 = 0;
-  LMKD_REQUIRE(!seg_n0 || g_conv_x3 || g_conv_bf16, "lmkd_conv2d_bwd_data_seg: two frame segments exist in the bf16-plane modes");
+  LMKD_REQUIRE(!seg_n0 || conv_planes(), "lmkd_conv2d_bwd_data_seg: two frame segments exist in the bf16-plane modes");
   LMKD_REQUIRE(Cout % 32 == 0, "lmkd_conv2d_bwd_data: Cout=%d must be a multiple of 32", Cout);
   LMKD_REQUIRE(stride == 1 || stride == 2, "lmkd_conv2d_bwd_data: stride %d unsupported", stride);
   LMKD_REQUIRE(KH * KW <= LMKD_MAX_TAPS, "lmkd_conv2d_bwd_data: kernel too large");
-  LMKD_REQUIRE(!g_lmkd_act_bf16 || g_conv_bf16, "bf16 activations need lmkd_conv_set_compute_dtype(1)");
+  LMKD_REQUIRE(!g_lmkd_act_bf16 || conv_nprod() == 1, "bf16 activations need lmkd_conv_set_compute_dtype(1)");
   const int Ho = conv_out(H, KH, stride, pad), Wo = conv_out(W, KW, stride, pad);
   LMKD_REQUIRE((long)N * H * W * Cin < 2147483647L && (long)N * Ho * Wo * Cout < 2147483647L,
                "lmkd_conv2d_bwd_data: tensor exceeds 2^31 elements");
-  LMKD_REQUIRE(!(g_conv_x3 || g_conv_bf16) || (long)N * Ho * Wo * Cout * (g_lmkd_act_bf16 ? 2 : 4) < 0xffffffe0L,
+  LMKD_REQUIRE(!conv_planes() || (long)N * Ho * Wo * Cout * (g_lmkd_act_bf16 ? 2 : 4) < 0xffffffe0L,
                "lmkd_conv2d_bwd_data: dy exceeds the 4 GiB buffer range of the bf16-plane kernels");
-  memset(&a, 0, sizeof(a));
-  a.src = dy; a.wpk = wd; a.out = dx; a.stat_partial = nullptr; a.accum = accumulate;
+  dgrad_geometry(a, N, H, W, Cin, Cout, KH, KW, stride, pad, seg_n0);
+  a.src = dy; a.wpk = wd; a.out = dx; a.accum = accumulate;
   a.h2_xw = am ? (const unsigned*)am->dy_words : nullptr;
-  a.N = N; a.Hs = Ho; a.Ws = Wo; a.Cs = Cout;
-  a.Ho = H; a.Wo = W; a.Co = Cin;
-  a.Kp = KH * KW * Cout; a.cps = Cout / 32;
-  a.sh = 1;
-  if (stride == 1) {
-    a.nclass = 1; a.omul = 1; a.Hr = H; a.Wr = W;
-    int nt = 0;
-    for (int kh = 0; kh < KH; ++kh)
-      for (int kw = 0; kw < KW; ++kw) a.taps[0][nt++] = Tap{pad - kh, pad - kw, (kh * KW + kw) * Cout};
-    a.ntap[0] = nt;
-  } else {
-    // rows enumerated per input parity (ph,pw): ih = 2a+ph, source oh = (ih + pad - kh)/2 = a + (ph+pad-kh)/2
-    a.nclass = 4; a.omul = 2; a.Hr = (H + 1) / 2; a.Wr = (W + 1) / 2;
-    for (int c = 0; c < 4; ++c) {
-      const int ph = c >> 1, pw = c & 1;
-      int nt = 0;
-      for (int kh = 0; kh < KH; ++kh) {
-        if (((ph + pad - kh) & 1) != 0) continue;
-        for (int kw = 0; kw < KW; ++kw) {
-          if (((pw + pad - kw) & 1) != 0) continue;
-          // floor division (numerator may be negative)
-          const int nh = ph + pad - kh, nw = pw + pad - kw;
-          a.taps[c][nt++] = Tap{nh >= 0 ? nh / 2 : -((-nh) / 2), nw >= 0 ? nw / 2 : -((-nw) / 2), (kh * KW + kw) * Cout};
-        }
-      }
-      a.ntap[c] = nt;
-    }
-  }
-  a.rows_per_class = N * a.Hr * a.Wr;
-  a.seg_m0 = seg_n0 * a.Hr * a.Wr;
-  a.tiles_per_class = cdiv(a.rows_per_class, 128);
-  a.div_hw = make_fastdiv(a.Hr * a.Wr); a.div_w = make_fastdiv(a.Wr);
-  a.same = patch_halo(a) >= 0 ? 1 : 0;
   return LMKD_OK;
 }
 
@@ -1508,7 +1547,7 @@ extern "C" int lmkd_conv2d_bwd_data(const float* dy, const float* wd, float* dx,
   LMKD_REQUIRE(aligned16(dy) && aligned16(wd), "lmkd_conv2d_bwd_data: operands must be 16-byte aligned");
   ConvGemmArgs a;
   if (const int rc = bwd_data_args(a, dy, wd, dx, N, H, W, Cin, Cout, KH, KW, stride, pad, accumulate)) return rc;
-  return launch_conv_gemm<false, 0>(a, Cin, (hipStream_t)stream);
+  return launch_conv(a, plan_dgrad(a), (hipStream_t)stream);
 }
 
 // The data gradient that feeds relu + train-mode BatchNorm backward (BasicBlock: d a1 = dgrad(conv2), a1 = relu(bn1(c1));
@@ -1516,20 +1555,14 @@ extern "C" int lmkd_conv2d_bwd_data(const float* dy, const float* wd, float* dx,
 // has just produced and leaves the per-row-tile sums (sum g, sum g * xhat) in `part`, so lmkd_bn_backward_part needs no reduction pass
 // over (dx, bn_x).  Exists for the launches conv_patch16_x3_kernel serves (stride 1, three-plane arithmetic, fp32 tensors, 128-row
 // tiles); lmkd_conv2d_bwd_data_bn_tiles returns the row count of `part` ([tiles][Cin][2] floats) or 0 when the launch has no such form.
-static bool bwd_data_bn_ok(const ConvGemmArgs& a, int Cin) {
-  if (!(g_patch16 && g_conv_x3 && !g_lmkd_act_bf16) || a.nclass != 1 || Cin % 4 != 0) return false;
-  if (patch_halo(a) < 0) return false;
-  const int id = pick_conv_cfg(a.rows_per_class, a.nclass, Cin, a.same != 0);
-  return id == 11 || id == 12;
-}
 extern "C" int lmkd_conv2d_bwd_data_bn_tiles_seg(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int seg_n0, int* tiles0) {
   if (stride != 1 || Cout % 32 != 0 || KH * KW > LMKD_MAX_TAPS) return 0;
   ConvGemmArgs a;
   if (bwd_data_args(a, nullptr, nullptr, nullptr, N, H, W, Cin, Cout, KH, KW, stride, pad, 0, seg_n0)) return 0;
-  if (!bwd_data_bn_ok(a, Cin)) return 0;
-  conv_set_tiles(a, 128);
-  if (tiles0) *tiles0 = a.seg_t0;
-  return a.tiles_per_class;
+  const ConvPlan p = plan_dgrad(a);
+  if (!p.bnb_form) return 0;
+  if (tiles0) *tiles0 = p.seg_t0;
+  return p.tiles_per_class;
 }
 extern "C" int lmkd_conv2d_bwd_data_bn_tiles(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad) {
   return lmkd_conv2d_bwd_data_bn_tiles_seg(N, H, W, Cin, Cout, KH, KW, stride, pad, 0, nullptr);
@@ -1547,10 +1580,11 @@ extern "C" int lmkd_conv2d_bwd_data_seg(const float* dy, const float* wd, float*
   note_fenced(amax);
   if (bn_x) {
     LMKD_REQUIRE(!accumulate && aligned16(bn_x) && aligned16(bn_stats), "lmkd_conv2d_bwd_data_seg: the fused BatchNorm sums need a plain (non-accumulating) launch and aligned operands");
-    LMKD_REQUIRE(bwd_data_bn_ok(a, Cin), "lmkd_conv2d_bwd_data_seg: this launch has no fused form (lmkd_conv2d_bwd_data_bn_tiles_seg returned 0)");
     a.bnb_x = bn_x; a.bnb_stats = bn_stats; a.stat_partial = part;
   }
-  return launch_conv_gemm<false, 0>(a, Cin, (hipStream_t)stream);
+  const ConvPlan p = plan_dgrad(a);
+  LMKD_REQUIRE(!bn_x || p.bnb_form, "lmkd_conv2d_bwd_data_seg: this launch has no fused form (lmkd_conv2d_bwd_data_bn_tiles_seg returned 0)");
+  return launch_conv(a, p, (hipStream_t)stream);
 }
 extern "C" int lmkd_conv2d_bwd_data_bn(const float* dy, const float* wd, float* dx, const float* bn_x, const float* bn_stats, float* part,
                                        int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, void* stream) {
@@ -1558,9 +1592,10 @@ extern "C" int lmkd_conv2d_bwd_data_bn(const float* dy, const float* wd, float* 
   LMKD_REQUIRE(aligned16(dy) && aligned16(wd) && aligned16(bn_x) && aligned16(bn_stats), "lmkd_conv2d_bwd_data_bn: operands must be 16-byte aligned");
   ConvGemmArgs a;
   if (const int rc = bwd_data_args(a, dy, wd, dx, N, H, W, Cin, Cout, KH, KW, stride, pad, 0)) return rc;
-  LMKD_REQUIRE(bwd_data_bn_ok(a, Cin), "lmkd_conv2d_bwd_data_bn: this launch has no fused form (lmkd_conv2d_bwd_data_bn_tiles returned 0)");
   a.bnb_x = bn_x; a.bnb_stats = bn_stats; a.stat_partial = part;
-  return launch_conv_gemm<false, 0>(a, Cin, (hipStream_t)stream);
+  const ConvPlan p = plan_dgrad(a);
+  LMKD_REQUIRE(p.bnb_form, "lmkd_conv2d_bwd_data_bn: this launch has no fused form (lmkd_conv2d_bwd_data_bn_tiles returned 0)");
+  return launch_conv(a, p, (hipStream_t)stream);
 }
 
 // Split-K plan of the weight gradient.  Output tiles are few (Cout x 9*Cin is small) and the reduction is long, so the
@@ -1574,7 +1609,7 @@ extern "C" int lmkd_conv_set_wgrad_win16(int on) { g_wgrad_win16 = on ? 1 : 0; r
 static int g_wgrad_window = 1;
 extern "C" int lmkd_conv_set_wgrad_window(int on) { g_wgrad_window = on < 0 ? 0 : on; return LMKD_OK; }      // > 1: workgroup target of the split plan
 static inline bool wgrad_win_eligible(int W, int Cs, int Cout, int KH, int KW, int stride, int pad) {
-  return g_wgrad_window && g_wgrad_planes && (g_conv_x3 || g_conv_bf16) && KH == 3 && KW == 3 && stride == 1 && pad == 1 &&
+  return g_wgrad_window && g_wgrad_planes && conv_planes() && KH == 3 && KW == 3 && stride == 1 && pad == 1 &&
          Cs % 32 == 0 && 32 + 2 * (W + 1) <= 256;
 }
 // pixel splits: ONE round of resident workgroups (two per CU; four of the two-wave workgroups of the one-plane modes - registers
@@ -1586,7 +1621,7 @@ static void wgrad_win_plan(int Mpix, int W, int Cs, int Cout, int* cob, int* spl
   const int tiles = cdiv(Cout, 32 * *cob) * (Cs / 32);
   const int steps = cdiv(Mpix, LMKD_BK);
   const int warm = cdiv(2 * (W + 1), LMKD_BK);
-  const int resident = 256 * ((g_conv_x3 && *cob == 2) ? 2 : 8 / *cob);
+  const int resident = 256 * ((conv_nprod() >= 6 && *cob == 2) ? 2 : 8 / *cob);
   // Round 5: the number of slabs is proportional to the segment's WORK, one round of resident workgroups for a whole 400-frame episode
   // (steps x tiles = 39 200 x 4 / cob on every 3x3 layer of the trunk), not one round per call: since round 4 the support and the query call are
   // ONE launch over two frame segments, each planned on its own (so that the merged and the two-call form stay bit-identical, the plan may
@@ -1600,7 +1635,6 @@ static void wgrad_win_plan(int Mpix, int W, int Cs, int Cout, int* cob, int* spl
   *steps_per_split = cdiv(steps, sp);
   *splits = cdiv(steps, *steps_per_split);
 }
-static inline bool wgrad_uses_planes(int Cs) { (void)Cs; return (g_conv_x3 || g_conv_bf16) && g_wgrad_planes; }
 
 static void wgrad_plan(int Mpix, int Cout, int Kp, int* splits, int* steps_per_split, int* bm, int* bn, bool planes = false) {
   // both operands are K-outer here (b32 fragment reads): the 128-wide tiles (1 read per MFMA) beat 64x64 (2 per MFMA):
@@ -1610,7 +1644,7 @@ static void wgrad_plan(int Mpix, int Cout, int Kp, int* splits, int* steps_per_s
   int per_cu = (*bm == 128 && *bn == 128) ? 2 : ((*bm == 64 && *bn == 64) ? 4 : 3);
   if (planes) {      // wgrad_x3.h: 4-wave workgroups, LDS = planes x 32 k rows x (2 bytes per column + 64) per operand
     if (*bm == 64 && *bn == 128) *bn = 64;
-    const int npl = g_conv_bf16 ? 1 : 3;
+    const int npl = conv_nprod() == 1 ? 1 : 3;
     const long lds = 1L * npl * LMKD_BK * ((*bm * 2 + 64) + (*bn * 2 + 64));      // single LDS buffer
     per_cu = (int)(160 * 1024 / lds);
     if (per_cu > 4) per_cu = 4;
@@ -1646,7 +1680,7 @@ static void wgrad_plan(int Mpix, int Cout, int Kp, int* splits, int* steps_per_s
 static int g_wgrad_stem = 1;
 extern "C" int lmkd_conv_set_wgrad_stem(int on) { g_wgrad_stem = on ? 1 : 0; return LMKD_OK; }
 static int stem_wgrad_plan(int N, int H, int W, int Cs, int Cout, int KH, int KW, int stride, int pad, int* G) {
-  if (!g_wgrad_stem || !g_wgrad_planes || !g_conv_x3 || g_lmkd_act_bf16 || Cs != 4 || Cout != 64 || KH != 7 || KW != 7 || stride != 2 || pad != 3) return 0;
+  if (!g_wgrad_stem || !g_wgrad_planes || conv_nprod(g_lmkd_act_bf16) < 6 || Cs != 4 || Cout != 64 || KH != 7 || KW != 7 || stride != 2 || pad != 3) return 0;
   const int Ho = conv_out(H, KH, stride, pad), Wo = conv_out(W, KW, stride, pad);
   if (Wo < 17 || Wo > 128 || W > 2 * Wo || Ho < 1) return 0;      // >= 2 steps of 32 pixels per unit; LDS: 60 * (16 Wo + 64) + 30720 bytes
   const int units = N * cdiv(Ho, 2);
@@ -1656,33 +1690,172 @@ static int stem_wgrad_plan(int N, int H, int W, int Cs, int Cout, int KH, int KW
   return cdiv(units, g);
 }
 
-// workspace of the two-segment form (lmkd_conv2d_bwd_weight_seg).  Each segment is split into the slabs a launch of its own would
-// use - the same partial sums (a slab's length bounds the MFMA accumulation error, wgrad_plan), twice the workgroups - so the
-// workspace is the sum of the two plans (or the one-launch plan where the kernel has no segments: the stem's)
-extern "C" long lmkd_conv2d_bwd_weight_workspace(int N, int H, int W, int Cs, int Cout, int KH, int KW, int stride, int pad);
-extern "C" long lmkd_conv2d_bwd_weight_workspace_seg(int N, int H, int W, int Cs, int Cout, int KH, int KW, int stride, int pad, int seg_n0) {
-  const long whole = lmkd_conv2d_bwd_weight_workspace(N, H, W, Cs, Cout, KH, KW, stride, pad);
-  if (seg_n0 <= 0 || seg_n0 >= N) return whole;
-  const long parts = lmkd_conv2d_bwd_weight_workspace(seg_n0, H, W, Cs, Cout, KH, KW, stride, pad) +
-                     lmkd_conv2d_bwd_weight_workspace(N - seg_n0, H, W, Cs, Cout, KH, KW, stride, pad);
-  return std::max(whole, parts);
-}
+// ---- weight-gradient plan --------------------------------------------------------------------------
+// Which kernel a weight gradient runs, with its pixel splits, grid and workspace: decided once, by plan_wgrad, for the launch
+// (launch_wgrad), the report (lmkd_conv2d_plan kind 2) and the workspace size (lmkd_conv2d_bwd_weight_workspace_seg).
+enum class WgFam : unsigned char {
+  Stem,       // stem_wgrad_kernel (wgrad_stem.h), reported as id 14
+  Win16,      // rolling window on the 16x16x32 MFMA (conv_wgrad_win16_kernel), ids 5 / 6 = 128 / 64 output channels per workgroup
+  Win,        // rolling window on the 32x32x16 MFMA (conv_wgrad_win_kernel), ids 5 / 6
+  Planes,     // bf16-plane im2col gather (conv_wgrad_x3_kernel), ids 1 - 4 by tile
+  Tile,       // fp32 MFMA tiles (conv_wgrad_kernel), ids 1 - 4 by tile
+};
+struct WgradPlan {
+  WgFam fam;
+  bool pre, act16, smallc;
+  int nprod;              // conv_nprod of the launch
+  int bm, bn;             // Planes / Tile: output tile (Cout x packed K)
+  int cob;                // Win16 / Win: 32-channel blocks of Cout per workgroup (COB)
+  int G;                  // Stem: units per slab
+  int splits, splits0, sps0, sps1, seg_pix0;      // pixel splits (all / of segment 0), K-steps per split of each segment, segment 0's pixels
+  int xcd;                // Planes / Tile: all tiles of a pixel split on one XCD
+  int grid;
+  long need;              // workspace bytes the launch writes
+  long ws;                // workspace bytes lmkd_conv2d_bwd_weight_workspace(_seg) reports
+};
 
-extern "C" long lmkd_conv2d_bwd_weight_workspace(int N, int H, int W, int Cs, int Cout, int KH, int KW, int stride, int pad) {
+// workspace of one launch without frame segments: the larger of the gather and the window kernel's split plans
+static long wgrad_workspace(int N, int H, int W, int Cs, int Cout, int KH, int KW, int stride, int pad) {
   const int Ho = conv_out(H, KH, stride, pad), Wo = conv_out(W, KW, stride, pad);
   const int Kp = KH * kw_padded(Cs, KW) * Cs;
-  {
-    int G;
-    if (const int slabs = stem_wgrad_plan(N, H, W, Cs, Cout, KH, KW, stride, pad, &G)) return (long)slabs * Cout * Kp * sizeof(float);
-  }
-  int splits, sps, bm, bn;
-  wgrad_plan(N * Ho * Wo, Cout, Kp, &splits, &sps, &bm, &bn, wgrad_uses_planes(Cs));
+  int G, splits, sps, bm, bn;
+  if (const int slabs = stem_wgrad_plan(N, H, W, Cs, Cout, KH, KW, stride, pad, &G)) return (long)slabs * Cout * Kp * sizeof(float);
+  wgrad_plan(N * Ho * Wo, Cout, Kp, &splits, &sps, &bm, &bn, conv_planes() && g_wgrad_planes);
   if (wgrad_win_eligible(W, Cs, Cout, KH, KW, stride, pad)) {
     int cob, wsplits, wsps;
     wgrad_win_plan(N * Ho * Wo, W, Cs, Cout, &cob, &wsplits, &wsps);
     splits = std::max(splits, wsplits);
   }
   return (long)splits * Cout * Kp * sizeof(float);
+}
+
+// seg_n0: two frame segments [0, seg_n0) | [seg_n0, N) (0: one); pre: relu(BatchNorm(x)) in the loader; maxima: the caller named max |x|
+// and max |dy|
+static WgradPlan plan_wgrad(int N, int H, int W, int Cs, int Cout, int KH, int KW, int stride, int pad, int seg_n0, bool pre, bool maxima) {
+  WgradPlan p;
+  memset(&p, 0, sizeof(p));
+  const bool act16 = g_lmkd_act_bf16;
+  const int Ho = conv_out(H, KH, stride, pad), Wo = conv_out(W, KW, stride, pad);
+  const int Kp = KH * kw_padded(Cs, KW) * Cs, Mpix = N * Ho * Wo;
+  p.pre = pre; p.act16 = act16; p.smallc = Cs == 4;
+  // each frame segment is split into the slabs a launch of its own would use - the same partial sums (a slab's length bounds the MFMA
+  // accumulation error, wgrad_plan), twice the workgroups - so the workspace is the larger of the whole launch's and the two segments'
+  // (the stem's kernel has no segments: its one-launch plan)
+  p.ws = wgrad_workspace(N, H, W, Cs, Cout, KH, KW, stride, pad);
+  if (seg_n0)
+    p.ws = std::max(p.ws, wgrad_workspace(seg_n0, H, W, Cs, Cout, KH, KW, stride, pad) + wgrad_workspace(N - seg_n0, H, W, Cs, Cout, KH, KW, stride, pad));
+  p.seg_pix0 = seg_n0 ? seg_n0 * Ho * Wo : Mpix;
+  if (const int slabs = stem_wgrad_plan(N, H, W, Cs, Cout, KH, KW, stride, pad, &p.G)) {
+    p.fam = WgFam::Stem;
+    p.nprod = conv_nprod(false, maxima);
+    // one workgroup per slab (the kernel can also walk several): a grid of exactly one resident workgroup per CU ran in TWO rounds
+    // whenever a CU was not free (583 us alone, erratic beside other streams)
+    p.splits = p.grid = slabs;
+  } else if (wgrad_win_eligible(W, Cs, Cout, KH, KW, stride, pad)) {
+    const bool w16 = g_wgrad_win16 && conv_nprod(act16) >= 6;      // three-plane modes, fp32 tensors: the 16x16x32 MFMA form
+    p.fam = w16 ? WgFam::Win16 : WgFam::Win;
+    p.nprod = w16 ? conv_nprod(false, maxima) : conv_nprod(act16);
+    wgrad_win_plan(Mpix, W, Cs, Cout, &p.cob, &p.splits, &p.sps0);
+    p.splits0 = p.splits;
+    if (seg_n0) {
+      int sp1, cob1;
+      wgrad_win_plan(p.seg_pix0, W, Cs, Cout, &p.cob, &p.splits0, &p.sps0);
+      wgrad_win_plan(Mpix - p.seg_pix0, W, Cs, Cout, &cob1, &sp1, &p.sps1);
+      p.splits = p.splits0 + sp1;
+    }
+    p.grid = 8 * cdiv(p.splits, 8) * cdiv(Cout, 32 * p.cob) * (Cs / 32);
+  } else {
+    const bool planes = conv_planes() && g_wgrad_planes;
+    p.fam = planes ? WgFam::Planes : WgFam::Tile;
+    // conv_wgrad_x3_kernel's two-plane form: not the padded stem input, not the BatchNorm loader
+    p.nprod = planes ? conv_nprod(act16, maxima && !p.smallc && !pre) : (conv_nprod() == 1 ? 1 : 0);      // (Tile: bf16 inputs in mode 1)
+    wgrad_plan(Mpix, Cout, Kp, &p.splits, &p.sps0, &p.bm, &p.bn, planes);
+    p.splits0 = p.splits;
+    if (seg_n0) {
+      int sp1, bm1, bn1;
+      wgrad_plan(p.seg_pix0, Cout, Kp, &p.splits0, &p.sps0, &p.bm, &p.bn, planes);
+      wgrad_plan(Mpix - p.seg_pix0, Cout, Kp, &sp1, &p.sps1, &bm1, &bn1, planes);      // (the tile shape depends on Cout and Kp only)
+      p.splits = p.splits0 + sp1;
+    }
+    // all column tiles of one pixel split read the same x / dy rows: with >= 32 splits they are dealt to ONE XCD (ids congruent
+    // mod 8), whose L2 then serves the re-reads.  PMC: FETCH_SIZE 1053 -> 279 MB per launch (algorithmic 160-320 MB); the kernel
+    // alone is a few % slower on layer 1, the two-stream episode is unchanged (20.5 episodes/s), so it is on by default;
+    // lmkd_conv_set_xcd_mode(1) keeps the plain order
+    p.xcd = (g_xcd_mode != 0 && g_xcd_mode != 1 && p.splits >= 32) ? 1 : 0;
+    p.grid = (p.xcd ? 8 * cdiv(p.splits, 8) : p.splits) * cdiv(Cout, p.bm) * cdiv(Kp, p.bn);
+  }
+  p.need = (long)p.splits * Cout * Kp * sizeof(float);
+  return p;
+}
+
+// stem_wgrad_kernel
+template <int NPROD, int D, int RLC>
+static void launch_stem_wgrad(const StemWgradArgs& w, dim3 grid, size_t lds, hipStream_t s) {
+  lds_attr_once<stem_wgrad_kernel<NPROD, D, RLC>>(160 * 1024);
+  hipLaunchKernelGGL((stem_wgrad_kernel<NPROD, D, RLC>), grid, dim3(512), lds, s, w);
+}
+template <int NPROD>
+static void launch_stem_wgrad(const StemWgradArgs& w, dim3 grid, size_t lds, hipStream_t s) {
+  const bool deep = cdiv(2 * w.Wo, 32) >= 6;      // dy tiles fetched six steps ahead (224-pixel images: seven steps per unit), else two
+  if (deep && w.RL == 1856) launch_stem_wgrad<NPROD, 6, 1856>(w, grid, lds, s);      // 224-pixel images
+  else if (deep) launch_stem_wgrad<NPROD, 6, 0>(w, grid, lds, s);
+  else launch_stem_wgrad<NPROD, 2, 0>(w, grid, lds, s);
+}
+// conv_wgrad_win16_kernel / conv_wgrad_win_kernel with COB channel blocks
+template <int COB>
+static void launch_wgrad_win(const WgradWinArgs& w, const WgradPlan& p, bool big, hipStream_t s) {
+  const dim3 grid(p.grid);
+  if (p.fam == WgFam::Win16) {
+    // Cout = 64 (two channel blocks): the second pair of waves takes the other 16 input channels of all nine taps
+    constexpr int JW = COB == 2 ? 1 : 2;
+    constexpr int NT = 64 * COB * (2 / JW);
+    with_nprod<3, 6, 9>(p.nprod, [&](auto np) {
+      if (big && p.pre) hipLaunchKernelGGL((conv_wgrad_win16_kernel<COB, np, 256, true, 9, JW>), grid, dim3(NT), 0, s, w);
+      else if (big) hipLaunchKernelGGL((conv_wgrad_win16_kernel<COB, np, 256, false, 9, JW>), grid, dim3(NT), 0, s, w);
+      else if (p.pre) hipLaunchKernelGGL((conv_wgrad_win16_kernel<COB, np, 128, true, 9, JW>), grid, dim3(NT), 0, s, w);
+      else hipLaunchKernelGGL((conv_wgrad_win16_kernel<COB, np, 128, false, 9, JW>), grid, dim3(NT), 0, s, w);
+    });
+    return;
+  }
+  auto go = [&](auto np, auto a16, auto pre) {
+    constexpr int NPROD = decltype(np)::value;
+    constexpr bool A16 = decltype(a16)::value, PRE = decltype(pre)::value;
+    // Cout = 64 leaves two channel blocks: in the three-plane modes the nine taps are dealt 5 + 4 to two wave groups (four waves
+    // instead of two: 262 vs 318 us at 200 frames); with one plane the extra dy-fragment reads cost more (119 vs 94)
+    constexpr int TPW = (COB == 2 && NPROD != 1) ? 5 : 9;
+    constexpr int NT = 64 * COB * ((9 + TPW - 1) / TPW);
+    if (big) hipLaunchKernelGGL((conv_wgrad_win_kernel<COB, NPROD, A16, 256, PRE, TPW>), grid, dim3(NT), 0, s, w);
+    else hipLaunchKernelGGL((conv_wgrad_win_kernel<COB, NPROD, A16, 128, PRE, TPW>), grid, dim3(NT), 0, s, w);
+  };
+  using T = std::true_type;
+  using F = std::false_type;
+  if (p.act16) go(std::integral_constant<int, 1>{}, T{}, F{});
+  else with_nprod<1, 6, 9>(p.nprod, [&](auto np) { if (p.pre) go(np, F{}, T{}); else go(np, F{}, F{}); });
+}
+
+// conv_wgrad_x3_kernel
+template <class CFG>
+static void launch_wgrad_planes(const WgradArgs& a, const WgradPlan& p, hipStream_t s) {
+  const dim3 grid(p.grid), block(256);
+  if (p.act16) {
+    if (p.smallc) hipLaunchKernelGGL((conv_wgrad_x3_kernel<CFG, true, 1, false, true>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((conv_wgrad_x3_kernel<CFG, false, 1, false, true>), grid, block, 0, s, a);
+  } else if (p.smallc) {
+    with_nprod<1, 6, 9>(p.nprod, [&](auto np) { hipLaunchKernelGGL((conv_wgrad_x3_kernel<CFG, true, np, false>), grid, block, 0, s, a); });
+  } else if (p.pre) {
+    with_nprod<1, 6, 9>(p.nprod, [&](auto np) { hipLaunchKernelGGL((conv_wgrad_x3_kernel<CFG, false, np, true>), grid, block, 0, s, a); });
+  } else {
+    with_nprod<1, 3, 6, 9>(p.nprod, [&](auto np) { hipLaunchKernelGGL((conv_wgrad_x3_kernel<CFG, false, np, false>), grid, block, 0, s, a); });
+  }
+}
+
+// conv_wgrad_kernel
+template <class CFG, bool SM, int THR>
+static void launch_wgrad_tile(const WgradArgs& a, const WgradPlan& p, hipStream_t s) {
+  const dim3 grid(p.grid);
+  if (p.nprod == 1) hipLaunchKernelGGL((conv_wgrad_kernel<CFG, SM, true>), grid, dim3(THR), 0, s, a);
+  else if (!SM && p.pre) hipLaunchKernelGGL((conv_wgrad_kernel<CFG, false, false, true>), grid, dim3(THR), 0, s, a);
+  else hipLaunchKernelGGL((conv_wgrad_kernel<CFG, SM, false>), grid, dim3(THR), 0, s, a);
 }
 
 // dw_oihw[Cout,Cin,KH,KW] from x[N,H,W,Cs] (Cs >= Cin channel-padded) and dy[N,Ho,Wo,Cout]
@@ -1696,222 +1869,101 @@ static int conv2d_bwd_weight_impl(const float* x, const float* pre_stats, const 
   // two frame segments: each is split into the slabs a launch of its own would use (same partial sums, same accumulation error), the
   // PRE loader takes the segment's BatchNorm table, ONE slab reduce sums everything
   if (seg_n0 <= 0 || seg_n0 >= N) seg_n0 = 0;
-  LMKD_REQUIRE(!seg_n0 || ((g_conv_x3 || g_conv_bf16) && g_wgrad_planes), "lmkd_conv2d_bwd_weight_seg: two frame segments exist in the bf16-plane modes");
   LMKD_REQUIRE(aligned16(x) && aligned16(dy) && aligned16(workspace), "lmkd_conv2d_bwd_weight: operands must be 16-byte aligned");
   LMKD_REQUIRE(Cs % 32 == 0 || Cs == 4, "lmkd_conv2d_bwd_weight: channel count %d must be 4 or a multiple of 32", Cs);
   LMKD_REQUIRE(Cout % 4 == 0, "lmkd_conv2d_bwd_weight: Cout %% 4 != 0");
   const bool smallc = Cs == 4;
-  LMKD_REQUIRE(!pre_stats || (!smallc && (!g_conv_bf16 || g_wgrad_planes) && !g_lmkd_act_bf16), "lmkd_conv2d_bwd_weight_pre: Cs %% 32 == 0, fp32 activations only");
-  LMKD_REQUIRE(!g_lmkd_act_bf16 || (g_conv_bf16 && g_wgrad_planes), "bf16 activations need lmkd_conv_set_compute_dtype(1) and the plane weight-gradient kernel");
+  const WgradPlan p = plan_wgrad(N, H, W, Cs, Cout, KH, KW, stride, pad, seg_n0, pre_stats != nullptr, amax_x && amax_dy);
+  LMKD_REQUIRE(!seg_n0 || p.fam != WgFam::Tile, "lmkd_conv2d_bwd_weight_seg: two frame segments exist in the bf16-plane modes");
+  LMKD_REQUIRE(!pre_stats || (!smallc && (conv_nprod() != 1 || p.fam != WgFam::Tile) && !p.act16), "lmkd_conv2d_bwd_weight_pre: Cs %% 32 == 0, fp32 activations only");
+  LMKD_REQUIRE(!p.act16 || (conv_nprod() == 1 && p.fam != WgFam::Tile), "bf16 activations need lmkd_conv_set_compute_dtype(1) and the plane weight-gradient kernel");
+  const int Ho = conv_out(H, KH, stride, pad), Wo = conv_out(W, KW, stride, pad);
+  const int KWp = kw_padded(Cs, KW), Kp = KH * KWp * Cs, Mpix = N * Ho * Wo;
+  LMKD_REQUIRE((long)N * H * W * Cs < 2147483647L && (long)Mpix * Cout < 2147483647L, "lmkd_conv2d_bwd_weight: tensor too large");
+  LMKD_REQUIRE(ws_bytes >= p.need, "lmkd_conv2d_bwd_weight: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  if (p.fam == WgFam::Stem) {
+    LMKD_REQUIRE((long)Mpix * 64 * 4 < 0xffffffe0L && (long)N * H * W * 16 < 0xffffffe0L, "lmkd_conv2d_bwd_weight: tensor too large for 32-bit byte offsets");
+    StemWgradArgs w;
+    memset(&w, 0, sizeof(w));
+    w.dy = dy; w.x = x; w.slab = workspace;
+    w.h2_xw = amax_x; w.h2_dyw = amax_dy;
+    w.N = N; w.H = H; w.W = W; w.Ho = Ho; w.Wo = Wo;
+    w.upi = cdiv(Ho, 2); w.units = N * w.upi; w.G = p.G; w.slabs = p.splits;
+    w.RL = 16 * Wo + 64;
+    const size_t lds = (size_t)2 * 10 * 3 * w.RL + 2 * 3 * STEM_WG_APLANE;
+    with_nprod<3, 6, 9>(p.nprod, [&](auto np) { launch_stem_wgrad<np>(w, dim3(p.grid), lds, s); });
+    LMKD_CHECK_LAUNCH("stem_wgrad_kernel");
+    if (Kp <= 256) {
+      hipLaunchKernelGGL(wgrad_reduce_stem_kernel, dim3(Cout), dim3(256, 4), 0, s, (const float*)workspace, dw_oihw, p.splits, Cout, Cin, Cs, KH, KW,
+                         KWp, Kp, accumulate);
+    } else {
+      launch_wgrad_reduce((const float*)workspace, dw_oihw, p.splits, Cout, Cin, Cs, KH, KW, KWp, Kp, accumulate, s);
+    }
+    LMKD_CHECK_LAUNCH("wgrad_reduce_kernel");
+    return LMKD_OK;
+  }
+  if (p.fam == WgFam::Win16 || p.fam == WgFam::Win) {
+    LMKD_REQUIRE((long)Mpix * std::max(Cs, Cout) * 4 < 2147483647L, "lmkd_conv2d_bwd_weight: tensor too large for 32-bit byte offsets");
+    WgradWinArgs w;
+    memset(&w, 0, sizeof(w));
+    w.dy = dy; w.x = x; w.slab = workspace; w.pre_stats = pre_stats;
+    w.h2_xw = amax_x; w.h2_dyw = amax_dy;
+    w.N = N; w.H = H; w.W = W; w.Cs = Cs; w.Co = Cout; w.Kp = Kp; w.Mpix = Mpix;
+    w.steps_total = cdiv(Mpix, LMKD_BK);
+    w.splits = p.splits; w.steps_per_split = p.sps0;
+    w.seg_pix0 = p.seg_pix0; w.seg_splits0 = p.splits0; w.sps1 = p.sps1;
+    w.n_ct = cdiv(Cout, 32 * p.cob); w.n_it = Cs / 32;
+    w.div_hw = make_fastdiv(H * W); w.div_w = make_fastdiv(W);
+    const bool big = 32 + 2 * (W + 1) > 128;      // ring of 256 pixel rows instead of 128
+    if (p.cob == 4) launch_wgrad_win<4>(w, p, big, s);
+    else launch_wgrad_win<2>(w, p, big, s);
+    LMKD_CHECK_LAUNCH("conv_wgrad_win_kernel");
+    launch_wgrad_reduce((const float*)workspace, dw_oihw, p.splits, Cout, Cin, Cs, KH, KW, KWp, Kp, accumulate, s);
+    LMKD_CHECK_LAUNCH("wgrad_reduce_kernel");
+    return LMKD_OK;
+  }
   WgradArgs a;
   memset(&a, 0, sizeof(a));
   a.dy = dy; a.x = x; a.slab = workspace; a.pre_stats = pre_stats;
   a.h2_xw = amax_x; a.h2_dyw = amax_dy;
   a.N = N; a.Hs = H; a.Ws = W; a.Cs = Cs;
-  a.Ho = conv_out(H, KH, stride, pad); a.Wo = conv_out(W, KW, stride, pad); a.Co = Cout;
-  a.stride = stride; a.pad = pad; a.KH = KH; a.KW = KW; a.KWp = kw_padded(Cs, KW);
-  a.Kp = KH * a.KWp * Cs;
-  a.Mpix = N * a.Ho * a.Wo;
-  LMKD_REQUIRE((long)N * H * W * Cs < 2147483647L && (long)a.Mpix * Cout < 2147483647L, "lmkd_conv2d_bwd_weight: tensor too large");
-  hipStream_t s = (hipStream_t)stream;
-  {
-    int G;
-    if (const int slabs = stem_wgrad_plan(N, H, W, Cs, Cout, KH, KW, stride, pad, &G)) {
-      LMKD_REQUIRE(ws_bytes >= (long)slabs * Cout * a.Kp * (long)sizeof(float), "lmkd_conv2d_bwd_weight: workspace too small");
-      LMKD_REQUIRE((long)a.Mpix * 64 * 4 < 0xffffffe0L && (long)N * H * W * 16 < 0xffffffe0L, "lmkd_conv2d_bwd_weight: tensor too large for 32-bit byte offsets");
-      StemWgradArgs w;
-      memset(&w, 0, sizeof(w));
-      w.dy = dy; w.x = x; w.slab = workspace;
-      w.h2_xw = amax_x; w.h2_dyw = amax_dy;
-      w.N = N; w.H = H; w.W = W; w.Ho = a.Ho; w.Wo = a.Wo;
-      w.upi = cdiv(a.Ho, 2); w.units = N * w.upi; w.G = G; w.slabs = slabs;
-      w.RL = 16 * a.Wo + 64;
-      const size_t lds = (size_t)2 * 10 * 3 * w.RL + 2 * 3 * STEM_WG_APLANE;
-      // one workgroup per slab (the kernel can also walk several): a grid of exactly one resident workgroup per CU ran in TWO rounds
-      // whenever a CU was not free (583 us alone, erratic beside other streams)
-      const dim3 grid(slabs);
-      const bool deep = cdiv(2 * a.Wo, 32) >= 6;      // dy tiles fetched six steps ahead (224-pixel images: seven steps per unit), else two
-#define LMKD_STEM_WG(NPROD, D, RLC)                                                                                                      \
-  do {                                                                                                                                   \
-    static std::atomic<unsigned long long> attr_done{0};                                                                                 \
-    lmkd_lds_attr_once(attr_done, reinterpret_cast<const void*>(&stem_wgrad_kernel<NPROD, D, RLC>), 160 * 1024);                         \
-    hipLaunchKernelGGL((stem_wgrad_kernel<NPROD, D, RLC>), grid, dim3(512), lds, s, w);                                                   \
-  } while (0)
-      if (g_conv_x3 == 9) {
-        if (deep && w.RL == 1856) LMKD_STEM_WG(9, 6, 1856);      // 224-pixel images
-        else if (deep) LMKD_STEM_WG(9, 6, 0);
-        else LMKD_STEM_WG(9, 2, 0);
-      } else if (g_conv_h2 && amax_x && amax_dy) {      // two fp16 planes, three products
-        if (deep && w.RL == 1856) LMKD_STEM_WG(3, 6, 1856);
-        else if (deep) LMKD_STEM_WG(3, 6, 0);
-        else LMKD_STEM_WG(3, 2, 0);
-        ++g_h2_launches;
-      } else {
-        if (deep && w.RL == 1856) LMKD_STEM_WG(6, 6, 1856);
-        else if (deep) LMKD_STEM_WG(6, 6, 0);
-        else LMKD_STEM_WG(6, 2, 0);
-      }
-#undef LMKD_STEM_WG
-      LMKD_CHECK_LAUNCH("stem_wgrad_kernel");
-      if (a.Kp <= 256) {
-        hipLaunchKernelGGL(wgrad_reduce_stem_kernel, dim3(Cout), dim3(256, 4), 0, s, (const float*)workspace, dw_oihw, slabs, Cout, Cin, Cs, KH, KW,
-                           a.KWp, a.Kp, accumulate);
-      } else {
-        launch_wgrad_reduce((const float*)workspace, dw_oihw, slabs, Cout, Cin, Cs, KH, KW, a.KWp, a.Kp, accumulate, s);
-      }
-      LMKD_CHECK_LAUNCH("wgrad_reduce_kernel");
-      return LMKD_OK;
-    }
-  }
-  if (wgrad_win_eligible(W, Cs, Cout, KH, KW, stride, pad)) {
-    WgradWinArgs w;
-    memset(&w, 0, sizeof(w));
-    w.dy = dy; w.x = x; w.slab = workspace; w.pre_stats = pre_stats;
-    w.h2_xw = amax_x; w.h2_dyw = amax_dy;
-    w.N = N; w.H = H; w.W = W; w.Cs = Cs; w.Co = Cout; w.Kp = a.Kp; w.Mpix = a.Mpix;
-    w.steps_total = cdiv(a.Mpix, LMKD_BK);
-    int cob;
-    wgrad_win_plan(a.Mpix, W, Cs, Cout, &cob, &w.splits, &w.steps_per_split);
-    w.seg_pix0 = a.Mpix; w.seg_splits0 = w.splits; w.sps1 = 0;
-    if (seg_n0) {
-      int sp0, sp1, cob1;
-      w.seg_pix0 = seg_n0 * a.Ho * a.Wo;
-      wgrad_win_plan(w.seg_pix0, W, Cs, Cout, &cob, &sp0, &w.steps_per_split);
-      wgrad_win_plan(a.Mpix - w.seg_pix0, W, Cs, Cout, &cob1, &sp1, &w.sps1);
-      w.seg_splits0 = sp0; w.splits = sp0 + sp1;
-    }
-    LMKD_REQUIRE(ws_bytes >= (long)w.splits * Cout * a.Kp * (long)sizeof(float), "lmkd_conv2d_bwd_weight: workspace too small");
-    LMKD_REQUIRE((long)a.Mpix * std::max(Cs, Cout) * 4 < 2147483647L, "lmkd_conv2d_bwd_weight: tensor too large for 32-bit byte offsets");
-    w.n_ct = cdiv(Cout, 32 * cob); w.n_it = Cs / 32;
-    w.div_hw = make_fastdiv(H * W); w.div_w = make_fastdiv(W);
-    const dim3 wgrid(8 * cdiv(w.splits, 8) * w.n_ct * w.n_it);
-    const bool big = 32 + 2 * (W + 1) > 128;      // ring of 256 pixel rows instead of 128
-#define LMKD_WIN(COB, NPROD, A16, PRE)                                                                                  \
-  do {                                                                                                                  \
-    /* Cout = 64 leaves two channel blocks: in the three-plane modes the nine taps are dealt 5 + 4 to two wave groups (four    \
-       waves instead of two: 262 vs 318 us at 200 frames); with one plane the extra dy-fragment reads cost more (119 vs 94) */ \
-    constexpr int TPW = (COB == 2 && NPROD != 1) ? 5 : 9;                                                               \
-    constexpr int NT = 64 * COB * ((9 + TPW - 1) / TPW);                                                                \
-    if (big) hipLaunchKernelGGL((conv_wgrad_win_kernel<COB, NPROD, A16, 256, PRE, TPW>), wgrid, dim3(NT), 0, s, w);     \
-    else hipLaunchKernelGGL((conv_wgrad_win_kernel<COB, NPROD, A16, 128, PRE, TPW>), wgrid, dim3(NT), 0, s, w);         \
-  } while (0)
-#define LMKD_WIN16(COB, NPROD, PRE)                                                                                     \
-  do {                                                                                                                  \
-    /* Cout = 64 (two channel blocks): the second pair of waves takes the other 16 input channels of all nine taps */   \
-    constexpr int JW = COB == 2 ? 1 : 2;                                                                                \
-    constexpr int NT = 64 * COB * (2 / JW);                                                                             \
-    if (big) hipLaunchKernelGGL((conv_wgrad_win16_kernel<COB, NPROD, 256, PRE, 9, JW>), wgrid, dim3(NT), 0, s, w);      \
-    else hipLaunchKernelGGL((conv_wgrad_win16_kernel<COB, NPROD, 128, PRE, 9, JW>), wgrid, dim3(NT), 0, s, w);          \
-  } while (0)
-#define LMKD_WIN_MODE(COB)                                                                                              \
-  do {                                                                                                                  \
-    if (g_wgrad_win16 && g_conv_x3 && !g_lmkd_act_bf16) {      /* three-plane modes, fp32 tensors: the 16x16x32 MFMA form */ \
-      if (g_conv_x3 == 9) { if (pre_stats) LMKD_WIN16(COB, 9, true); else LMKD_WIN16(COB, 9, false); }                  \
-      else if (g_conv_h2 && w.h2_xw && w.h2_dyw) {                                                                      \
-        if (pre_stats) LMKD_WIN16(COB, 3, true); else LMKD_WIN16(COB, 3, false);                                        \
-        ++g_h2_launches;                                                                                                \
-      }                                                                                                                 \
-      else { if (pre_stats) LMKD_WIN16(COB, 6, true); else LMKD_WIN16(COB, 6, false); }                                 \
-      break;                                                                                                            \
-    }                                                                                                                   \
-    if (g_lmkd_act_bf16) LMKD_WIN(COB, 1, true, false);                                                                 \
-    else if (g_conv_bf16) { if (pre_stats) LMKD_WIN(COB, 1, false, true); else LMKD_WIN(COB, 1, false, false); }        \
-    else if (g_conv_x3 == 9) { if (pre_stats) LMKD_WIN(COB, 9, false, true); else LMKD_WIN(COB, 9, false, false); }     \
-    else { if (pre_stats) LMKD_WIN(COB, 6, false, true); else LMKD_WIN(COB, 6, false, false); }                         \
-  } while (0)
-    if (cob == 4) LMKD_WIN_MODE(4);
-    else LMKD_WIN_MODE(2);
-#undef LMKD_WIN_MODE
-#undef LMKD_WIN16
-#undef LMKD_WIN
-    LMKD_CHECK_LAUNCH("conv_wgrad_win_kernel");
-    launch_wgrad_reduce((const float*)workspace, dw_oihw, w.splits, Cout, Cin, Cs, KH, KW, a.KWp, a.Kp, accumulate, s);
-    LMKD_CHECK_LAUNCH("wgrad_reduce_kernel");
-    return LMKD_OK;
-  }
-  int splits, bm, bn;
-  const bool planes = wgrad_uses_planes(Cs);
-  wgrad_plan(a.Mpix, Cout, a.Kp, &splits, &a.steps_per_split, &bm, &bn, planes);
-  a.seg_pix0 = a.Mpix; a.seg_splits0 = splits; a.sps1 = 0;
-  if (seg_n0) {
-    LMKD_REQUIRE(planes, "lmkd_conv2d_bwd_weight_seg: the fp32-tile kernel has no two-segment form");
-    int sp0, sp1, bm1, bn1;
-    a.seg_pix0 = seg_n0 * a.Ho * a.Wo;
-    wgrad_plan(a.seg_pix0, Cout, a.Kp, &sp0, &a.steps_per_split, &bm, &bn, planes);
-    wgrad_plan(a.Mpix - a.seg_pix0, Cout, a.Kp, &sp1, &a.sps1, &bm1, &bn1, planes);      // (the tile shape depends on Cout and Kp only)
-    a.seg_splits0 = sp0; splits = sp0 + sp1;
-  }
-  a.steps_total = cdiv(a.Mpix, LMKD_BK);
-  LMKD_REQUIRE(ws_bytes >= (long)splits * Cout * a.Kp * (long)sizeof(float), "lmkd_conv2d_bwd_weight: workspace too small");
-  a.div_hw = make_fastdiv(a.Ho * a.Wo); a.div_w = make_fastdiv(a.Wo);
-  a.n_mt = cdiv(Cout, bm); a.n_jt = cdiv(a.Kp, bn); a.splits = splits;
-  // all column tiles of one pixel split read the same x / dy rows: with >= 32 splits they are dealt to ONE XCD (ids congruent
-  // mod 8), whose L2 then serves the re-reads.  PMC: FETCH_SIZE 1053 -> 279 MB per launch (algorithmic 160-320 MB); the kernel
-  // alone is a few % slower on layer 1, the two-stream episode is unchanged (20.5 episodes/s), so it is on by default;
-  // lmkd_conv_set_xcd_mode(1) keeps the plain order
-  a.xcd_mode = (g_xcd_mode != 0 && g_xcd_mode != 1 && splits >= 32) ? 1 : 0;
-  dim3 grid((a.xcd_mode ? 8 * cdiv(splits, 8) : splits) * a.n_mt * a.n_jt);
-#define LMKD_WGRAD_LAUNCH(CFG, SM, THR)                                                                       \
-  do {                                                                                                          \
-    if (g_conv_bf16) hipLaunchKernelGGL((conv_wgrad_kernel<CFG, SM, true>), grid, dim3(THR), 0, s, a);          \
-    else if (!SM && pre_stats) hipLaunchKernelGGL((conv_wgrad_kernel<CFG, false, false, true>), grid, dim3(THR), 0, s, a); \
-    else hipLaunchKernelGGL((conv_wgrad_kernel<CFG, SM, false>), grid, dim3(THR), 0, s, a);                     \
-  } while (0)
-  if (planes) {
-#define LMKD_WGX3(CFG)                                                                                                   \
-  do {                                                                                                                   \
-    if (g_lmkd_act_bf16) {                                                                                               \
-      if (smallc) hipLaunchKernelGGL((conv_wgrad_x3_kernel<CFG, true, 1, false, true>), grid, dim3(256), 0, s, a);      \
-      else hipLaunchKernelGGL((conv_wgrad_x3_kernel<CFG, false, 1, false, true>), grid, dim3(256), 0, s, a);            \
-    } else if (smallc) {                                                                                                 \
-      if (g_conv_bf16) hipLaunchKernelGGL((conv_wgrad_x3_kernel<CFG, true, 1, false>), grid, dim3(256), 0, s, a);       \
-      else if (g_conv_x3 == 9) hipLaunchKernelGGL((conv_wgrad_x3_kernel<CFG, true, 9, false>), grid, dim3(256), 0, s, a); \
-      else hipLaunchKernelGGL((conv_wgrad_x3_kernel<CFG, true, 6, false>), grid, dim3(256), 0, s, a);                    \
-    } else if (g_conv_bf16) {                                                                                            \
-      if (pre_stats) hipLaunchKernelGGL((conv_wgrad_x3_kernel<CFG, false, 1, true>), grid, dim3(256), 0, s, a);         \
-      else hipLaunchKernelGGL((conv_wgrad_x3_kernel<CFG, false, 1, false>), grid, dim3(256), 0, s, a);                  \
-    } else if (g_conv_x3 == 9) {                                                                                         \
-      if (pre_stats) hipLaunchKernelGGL((conv_wgrad_x3_kernel<CFG, false, 9, true>), grid, dim3(256), 0, s, a);         \
-      else hipLaunchKernelGGL((conv_wgrad_x3_kernel<CFG, false, 9, false>), grid, dim3(256), 0, s, a);                  \
-    } else {                                                                                                             \
-      if (pre_stats) hipLaunchKernelGGL((conv_wgrad_x3_kernel<CFG, false, 6, true>), grid, dim3(256), 0, s, a);         \
-      else if (g_conv_h2 && a.h2_xw && a.h2_dyw) {                                                                      \
-        hipLaunchKernelGGL((conv_wgrad_x3_kernel<CFG, false, 3, false>), grid, dim3(256), 0, s, a);                      \
-        ++g_h2_launches;                                                                                                 \
-      } else hipLaunchKernelGGL((conv_wgrad_x3_kernel<CFG, false, 6, false>), grid, dim3(256), 0, s, a);                 \
-    }                                                                                                                    \
-  } while (0)
-    using W128 = WgCfg<128, 128, 2, 2>;
-    using W128x64 = WgCfg<128, 64, 2, 2>;
-    using W64 = WgCfg<64, 64, 2, 2>;
-    LMKD_REQUIRE(!smallc || (bm == 64 && bn == 64), "lmkd_conv2d_bwd_weight: padded-stem path expects Cout <= 64");
-    if (bm == 128 && bn == 128) LMKD_WGX3(W128);
-    else if (bm == 128) LMKD_WGX3(W128x64);
-    else LMKD_WGX3(W64);
-#undef LMKD_WGX3
+  a.Ho = Ho; a.Wo = Wo; a.Co = Cout;
+  a.stride = stride; a.pad = pad; a.KH = KH; a.KW = KW; a.KWp = KWp;
+  a.Kp = Kp; a.Mpix = Mpix;
+  a.steps_per_split = p.sps0;
+  a.seg_pix0 = p.seg_pix0; a.seg_splits0 = p.splits0; a.sps1 = p.sps1;
+  a.steps_total = cdiv(Mpix, LMKD_BK);
+  a.div_hw = make_fastdiv(Ho * Wo); a.div_w = make_fastdiv(Wo);
+  a.n_mt = cdiv(Cout, p.bm); a.n_jt = cdiv(Kp, p.bn); a.splits = p.splits;
+  a.xcd_mode = p.xcd;
+  const int bm = p.bm, bn = p.bn;
+  LMKD_REQUIRE(!smallc || (bm == 64 && bn == 64), "lmkd_conv2d_bwd_weight: padded-stem path expects Cout <= 64");
+  if (p.fam == WgFam::Planes) {
+    if (bm == 128 && bn == 128) launch_wgrad_planes<WgCfg<128, 128, 2, 2>>(a, p, s);
+    else if (bm == 128) launch_wgrad_planes<WgCfg<128, 64, 2, 2>>(a, p, s);
+    else launch_wgrad_planes<WgCfg<64, 64, 2, 2>>(a, p, s);
     LMKD_CHECK_LAUNCH("conv_wgrad_x3_kernel");
   } else {
-  using C64 = TileCfg<64, 64, 2, 2>;
-  using C128x64 = TileCfg<128, 64, 2, 2>;
-  using C64x128 = TileCfg<64, 128, 2, 2>;
-  using C128 = TileCfg<128, 128, 2, 4>;     // 8 waves: 4 per SIMD at 2 workgroups per CU
-  if (smallc) {
-    LMKD_REQUIRE(bm == 64 && bn == 64, "lmkd_conv2d_bwd_weight: padded-stem path expects Cout <= 64");
-    LMKD_WGRAD_LAUNCH(C64, true, LMKD_THREADS);
-  } else if (bm == 64 && bn == 64) {
-    LMKD_WGRAD_LAUNCH(C64, false, LMKD_THREADS);
-  } else if (bm == 128 && bn == 64) {
-    LMKD_WGRAD_LAUNCH(C128x64, false, LMKD_THREADS);
-  } else if (bm == 64 && bn == 128) {
-    LMKD_WGRAD_LAUNCH(C64x128, false, LMKD_THREADS);
-  } else {
-    LMKD_WGRAD_LAUNCH(C128, false, 512);
+    if (smallc) launch_wgrad_tile<TileCfg<64, 64, 2, 2>, true, LMKD_THREADS>(a, p, s);
+    else if (bm == 64 && bn == 64) launch_wgrad_tile<TileCfg<64, 64, 2, 2>, false, LMKD_THREADS>(a, p, s);
+    else if (bm == 128 && bn == 64) launch_wgrad_tile<TileCfg<128, 64, 2, 2>, false, LMKD_THREADS>(a, p, s);
+    else if (bm == 64 && bn == 128) launch_wgrad_tile<TileCfg<64, 128, 2, 2>, false, LMKD_THREADS>(a, p, s);
+    else launch_wgrad_tile<TileCfg<128, 128, 2, 4>, false, 512>(a, p, s);      // 8 waves: 4 per SIMD at 2 workgroups per CU
+    LMKD_CHECK_LAUNCH("conv_wgrad_kernel");
   }
-  LMKD_CHECK_LAUNCH("conv_wgrad_kernel");
-  }
-  launch_wgrad_reduce((const float*)workspace, dw_oihw, splits, Cout, Cin, Cs, KH, KW, a.KWp, a.Kp, accumulate, s);      // (stride-2 3x3 and 1x1 layers)
+  launch_wgrad_reduce((const float*)workspace, dw_oihw, p.splits, Cout, Cin, Cs, KH, KW, KWp, Kp, accumulate, s);      // (stride-2 3x3 and 1x1 layers)
   LMKD_CHECK_LAUNCH("wgrad_reduce_kernel");
   return LMKD_OK;
+}
+
+// workspace of lmkd_conv2d_bwd_weight (and of the two-segment form, lmkd_conv2d_bwd_weight_seg: plan_wgrad)
+extern "C" long lmkd_conv2d_bwd_weight_workspace_seg(int N, int H, int W, int Cs, int Cout, int KH, int KW, int stride, int pad, int seg_n0) {
+  if (seg_n0 <= 0 || seg_n0 >= N) seg_n0 = 0;
+  return plan_wgrad(N, H, W, Cs, Cout, KH, KW, stride, pad, seg_n0, false, false).ws;
+}
+extern "C" long lmkd_conv2d_bwd_weight_workspace(int N, int H, int W, int Cs, int Cout, int KH, int KW, int stride, int pad) {
+  return lmkd_conv2d_bwd_weight_workspace_seg(N, H, W, Cs, Cout, KH, KW, stride, pad, 0);
 }
 
 extern "C" int lmkd_conv2d_bwd_weight(const float* x, const float* dy, float* dw_oihw, float* workspace, long ws_bytes,
@@ -1947,23 +1999,6 @@ extern "C" int lmkd_conv2d_bwd_weight_seg(const float* x, const float* pre_stats
   return conv2d_bwd_weight_impl(x, pre_stats, dy, dw_oihw, workspace, ws_bytes, N, H, W, Cs, Cin, Cout, KH, KW, stride, pad, stream, accumulate, seg_n0, amax);
 }
 
-// stride-2 data gradient: does the LDS-patch kernel run its four parity classes (patch_halo() of the launch's arguments >= 0)?
-static bool dgrad_s2_patch_ok(int H, int W, int Cout, int KH, int KW, int pad) {
-  if (!g_conv_patch || !(g_conv_x3 || g_conv_bf16) || Cout % 32 != 0) return false;
-  const int Hr = (H + 1) / 2, Wr = (W + 1) / 2;
-  if (conv_out(H, KH, 2, pad) != Hr || conv_out(W, KW, 2, pad) != Wr) return false;
-  int halo = 0;
-  for (int c = 0; c < 4; ++c)
-    for (int kh = 0; kh < KH; ++kh)
-      for (int kw = 0; kw < KW; ++kw) {
-        const int nh = (c >> 1) + pad - kh, nw = (c & 1) + pad - kw;
-        if ((nh & 1) || (nw & 1)) continue;
-        const int sft = (nh >= 0 ? nh / 2 : -((-nh) / 2)) * Wr + (nw >= 0 ? nw / 2 : -((-nw) / 2));
-        halo = std::max(halo, sft < 0 ? -sft : sft);
-      }
-  return halo <= PATCH_HALO_MAX;
-}
-
 // Launch plan of a convolution, without launching: which kernel instance and tile order the three entry points above would
 // pick for these shapes in the current arithmetic mode (info: 5 ints).  info[0] = tile id (lmkd_conv_set_tile numbering; the weight gradient
 // reports 1 = 128x128/8 waves, 2 = 128x64, 3 = 64x64, 4 = 64x128), info[1] = XCD tile order (forward / data gradient: 0 row
@@ -1971,50 +2006,28 @@ static bool dgrad_s2_patch_ok(int H, int W, int Cout, int KH, int KW, int pad) {
 // or parity classes (data gradient), info[3] = workgroups launched.  Used by the parity tests to prove that the benchmark's
 // kernel instances are the ones under test.  info[4] = 1 when the launch runs on the LDS-patch kernel (conv_patch.h) or, for the
 // weight gradient, on the rolling-window kernel (wgrad_win.h; it reports tile id 5 = 128 output channels per workgroup, 6 = 64);
-// info[4] = 2: the stem's input-row patch kernel (conv_stem.h).
+// info[4] = 2: the stem's kernels, tile id 14 - the input-row patch kernel (conv_stem.h; info[2] = 1) and the weight gradient's
+// stem_wgrad_kernel (wgrad_stem.h; info[2] = slabs).
 extern "C" int lmkd_conv2d_plan(int kind, int N, int H, int W, int Cs, int Cin, int Cout, int KH, int KW, int stride, int pad,
                                 int* info) {
   LMKD_REQUIRE(info && kind >= 0 && kind <= 2, "lmkd_conv2d_plan: kind must be 0 (forward), 1 (data gradient) or 2 (weight gradient)");
   LMKD_REQUIRE(N > 0 && H > 0 && W > 0 && Cout > 0 && KH > 0 && KW > 0 && stride > 0, "lmkd_conv2d_plan: bad shape");
-  const int Ho = conv_out(H, KH, stride, pad), Wo = conv_out(W, KW, stride, pad);
   if (kind == 2) {
-    const int Kp = KH * kw_padded(Cs, KW) * Cs;
-    int splits, sps, bm, bn;
-    wgrad_plan(N * Ho * Wo, Cout, Kp, &splits, &sps, &bm, &bn, wgrad_uses_planes(Cs));
-    info[0] = (bm == 128 && bn == 128) ? 1 : (bm == 128 ? 2 : (bn == 128 ? 4 : 3));
-    info[1] = (g_xcd_mode != 0 && g_xcd_mode != 1 && splits >= 32) ? 1 : 0;
-    info[2] = splits;
-    info[3] = (info[1] ? 8 * cdiv(splits, 8) : splits) * cdiv(Cout, bm) * cdiv(Kp, bn);
-    info[4] = 0;
-    if (wgrad_win_eligible(W, Cs, Cout, KH, KW, stride, pad)) {      // rolling-window kernel (wgrad_win.h): tile id 5 / 6 = 128 / 64 output channels
-      int cob, wsplits, wsps;
-      wgrad_win_plan(N * Ho * Wo, W, Cs, Cout, &cob, &wsplits, &wsps);
-      info[0] = cob == 4 ? 5 : 6; info[1] = 1; info[2] = wsplits;
-      info[3] = 8 * cdiv(wsplits, 8) * cdiv(Cout, 32 * cob) * (Cs / 32);
-      info[4] = 1;
+    const WgradPlan p = plan_wgrad(N, H, W, Cs, Cout, KH, KW, stride, pad, 0, false, false);
+    info[1] = p.xcd; info[2] = p.splits; info[3] = p.grid;
+    switch (p.fam) {
+      case WgFam::Stem: info[0] = 14; info[4] = 2; break;
+      case WgFam::Win16:
+      case WgFam::Win: info[0] = p.cob == 4 ? 5 : 6; info[1] = 1; info[4] = 1; break;
+      default: info[0] = (p.bm == 128 && p.bn == 128) ? 1 : (p.bm == 128 ? 2 : (p.bn == 128 ? 4 : 3)); info[4] = 0; break;
     }
     return LMKD_OK;
   }
-  if (kind == 0 && stem_patch_pitch(W, Cs, Cout, KH, KW, stride, pad)) {      // conv_stem_patch_kernel: tile id 14, one workgroup per output row pair
-    info[0] = 14; info[1] = 0; info[2] = 1; info[3] = N * cdiv(Ho, 2); info[4] = 2;
-    return LMKD_OK;
-  }
-  long rows;
-  int nclass = 1, ncols;
-  if (kind == 0) { rows = (long)N * Ho * Wo; ncols = Cout; }
-  else {
-    ncols = Cin;
-    if (stride == 1) rows = (long)N * H * W;
-    else { nclass = 4; rows = (long)N * ((H + 1) / 2) * ((W + 1) / 2); }
-  }
-  const bool s2patch = kind == 1 && stride == 2 && dgrad_s2_patch_ok(H, W, Cout, KH, KW, pad);
-  const bool same = conv_same_size(H, W, KH, KW, stride, pad) || s2patch || (kind == 0 && fwd_s2_patch_ok(N, H, W, Cs, Cout, KH, KW, stride, pad));
-  int id = pick_conv_cfg(rows, nclass, ncols, same);
-  const bool patch = same && (g_conv_x3 || g_conv_bf16) && (kind == 0 ? Cs : Cout) % 32 == 0;      // patch_halo() >= 0 for these launches
-  if (!patch) id = id == 10 ? 7 : (id == 11 ? 9 : (id == 12 ? 8 : id));
-  const int n_rt = nclass * cdiv(rows, cfg_bm(id)), n_ct = cdiv(ncols, cfg_bn(id));
-  int xm = (n_ct >= 8 && (n_ct & 7) == 0) ? 1 : 0;
-  if (g_xcd_mode == 0) xm = 0;
-  info[0] = id; info[1] = xm; info[2] = nclass; info[3] = xcd_grid(n_rt, n_ct, xm); info[4] = patch ? 1 : 0;
+  ConvGemmArgs a;
+  if (kind == 0) fwd_geometry(a, N, H, W, Cs, Cout, KH, KW, stride, pad, 0);
+  else dgrad_geometry(a, N, H, W, Cin, Cout, KH, KW, stride, pad, 0);
+  const ConvPlan p = kind == 0 ? plan_fwd(a, KH, KW, pad) : plan_dgrad(a);
+  info[0] = p.tile; info[1] = p.xcd; info[2] = p.nclass; info[3] = p.grid;
+  info[4] = p.fam == ConvFam::Stem ? 2 : (p.fam == ConvFam::Patch || p.fam == ConvFam::Patch16 || p.fam == ConvFam::Patch1p ? 1 : 0);
   return LMKD_OK;
 }

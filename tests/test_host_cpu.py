@@ -367,3 +367,28 @@ def test_schedule_object_on_cpu():
         assert Schedule.current() == ser
     finally:
         before.apply()
+
+
+def test_conv_plan_reports_match_golden():
+    """the convolution plan entry points (lmkd_conv2d_plan kinds 0 / 1 / 2, the forward row tiles, the fused data-gradient BatchNorm
+    tiles, the weight-gradient workspace; one- and two-segment forms) over the ResNet-18 / ResNet-50 trunk shapes at 200 and 400
+    frames, in every arithmetic mode, with each dispatch switch flipped alone and each valid tile override: exactly the values
+    recorded in tests/golden/conv_plan.json.gz (tools/gen_conv_plan_golden.py).  Pure host code; every switch is restored after."""
+    import gzip
+    import importlib.util
+    import litemkd_amd
+    spec = importlib.util.spec_from_file_location("gen_conv_plan_golden", os.path.join(ROOT, "tools", "gen_conv_plan_golden.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    with gzip.open(os.path.join(ROOT, "tests", "golden", "conv_plan.json.gz"), "rt") as f:
+        want = json.load(f)
+    got = gen.sweep(litemkd_amd.lib())
+    assert set(got) == set(want)
+    bad = []
+    for st, rows in want.items():
+        assert set(got[st]) == set(rows), st
+        for sk, v in rows.items():
+            for f, a, b in zip(gen.FIELDS, got[st][sk], v):
+                if a != b:
+                    bad.append("%s | %s | %s: %d, golden %d" % (st, sk, f, a, b))
+    assert not bad, "%d differences:\n%s" % (len(bad), "\n".join(bad[:40]))
