@@ -10,8 +10,11 @@ N>1: one rank per GPU over RCCL.  Either the driver launches the ranks (python -
 bench.py --gpus N ...: RANK / WORLD_SIZE are then in the environment), or a plain `python bench.py --gpus N` starts them itself
 as a CHILD `python -m torch.distributed.run` process — before this process has made any GPU call — and exits with its code.
 
-Prints ONE JSON line (rank 0) with `roofline` (conv MFMA kernel, HIP-event timed inside the timed region)
-and `cpu_baseline` (the CPU oracle timed on this box's host cores, rank 0, N=1 only)."""
+Prints ONE JSON line (rank 0).  A plain run does only what that line's headline needs: set-up, allocator priming, the W warm-up
+steps, the K timed steps, --dump-outputs, the line.  `--full` adds everything else the benchmark measures, each in runs of its own
+after the timed region: `repeat` (the K steps again), `host_enqueue_ms_per_episode`, the per-kernel `roofline` of serialized episodes
+(with --serial the timed region itself), `other_modes` (the same job in the other arithmetics, N=1) and `cpu_baseline` (the CPU oracle
+timed on the host's cores, rank 0, N=1 only)."""
 import argparse
 import json
 import os
@@ -61,12 +64,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--shot", type=int, default=5)
     ap.add_argument("--pool", type=int, default=2, help="distinct resident synthetic episodes to cycle through")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the headline measurement also run what it does not need: the repeat of the "
+                    "timed steps, the host-enqueue probe, the per-kernel roofline pass, the other arithmetic modes and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--prime", type=int, default=160, help="at most this many untimed allocator-priming episodes in front of the warm-up (0: none)")
     ap.add_argument("--dropout", type=float, default=0.1, help="TRX dropout (reference default 0.1, active in train mode)")
     ap.add_argument("--serial", action="store_true", help="queue the two trunk calls on ONE stream (no kernel overlap); use this "
                     "mode under rocprofv3 so per-kernel durations are not inflated by concurrent kernels")
-    ap.add_argument("--roofline-episodes", type=int, default=2)
+    ap.add_argument("--roofline-episodes", type=int, default=2, help="serialized episodes of the roofline pass (--full, --layer-table)")
     ap.add_argument("--dtype", choices=["f32", "f32native", "bf16", "bf16conv", "f32x3"], default="f32", help="f32 (headline, BASELINE "
                     "configs[1]): fp32 tensors, fp32 accumulation; f32x3's arithmetic with the trunk's convolution kernels (3x3 forward and data "
                     "gradient, every weight gradient, the stem: 97 %% of the trunk's flops) on TWO fp16 planes + power-of-two scales, three products per fp32 "
@@ -74,19 +79,20 @@ def main():
                     "profiles/r04_h2_error.txt); f32x3 (rounds 2-3's headline, the library default): the convolution products on the bf16 "
                     "matrix pipe from an EXACT 3-way bf16 split of both operands, 6 products per fp32 product (csrc/conv_x3.h, wgrad_x3.h; "
                     "error vs fp64 of the class of the native fp32 MFMA: tests/test_gpu_fullsize.py); f32native: the same "
-                    "job on v_mfma_f32_32x32x2_f32 (round 1's headline arithmetic, reported under other_modes by default); "
+                    "job on v_mfma_f32_32x32x2_f32 (round 1's headline arithmetic, reported under other_modes with --full); "
                     "bf16 (configs[2]): bf16 tensors in HBM for every activation / activation gradient of the trunk, bf16 MFMA with "
                     "fp32 accumulation, fp32 statistics, weights and heads; bf16conv: round 1's variant (fp32 tensors, only the "
                     "convolution operands rounded)")
     ap.add_argument("--xcd-mode", type=int, default=-1, help="tuning: lmkd_conv_set_xcd_mode (-1 auto, 0 plain tile orders, 1 auto without XCD-grouped weight-gradient splits)")
-    ap.add_argument("--no-other-modes", action="store_true", help="skip the short bf16 / f32x3 side measurements of the default run")
+    ap.add_argument("--no-other-modes", action="store_true", help="--full without the short bf16 / f32x3 side measurements")
     ap.add_argument("--ew-wg", type=int, default=0, help="tuning: workgroups per CU of the HBM-bound kernels (lmkd_set_elementwise_wg_per_cu), 0 = default")
-    ap.add_argument("--layer-table", action="store_true", help="print the per-layer-shape conv timing table of the roofline pass to stderr")
+    ap.add_argument("--layer-table", action="store_true", help="print the per-layer-shape conv timing table of the roofline pass to stderr "
+                    "(runs that pass without --full too)")
     ap.add_argument("--tile", type=int, default=0, help="tuning: force a conv tile configuration (lmkd_conv_set_tile), 0 = auto")
     ap.add_argument("--backbone", default="resnet18_2fc", help="resnet18_2fc (headline) or resnet50_2fc (BASELINE configs[4])")
     ap.add_argument("--live-mfm", action="store_true", help="fuse rgb/depth/flow teacher features with the MFM transformer "
                     "inside every episode (BASELINE configs[4]) instead of using precomputed fused features")
-    ap.add_argument("--cpu-episodes", type=int, default=3, help="episodes of the bounded cpu_baseline sample")
+    ap.add_argument("--cpu-episodes", type=int, default=3, help="episodes of the bounded cpu_baseline sample (--full)")
     ap.add_argument("--graph", dest="graph", action="store_true", default=os.environ.get("LMKD_GRAPH", "0") == "1",
                     help="replay each resident episode as a captured hipGraph (trainloop.GraphedEpisode).  Same kernels, bit-identical results; "
                          "the ~560 launches of an episode leave the host path (1.3-2.0 ms of host time per episode instead of 8-11).  OFF by "
@@ -312,27 +318,29 @@ def main():
     if a.dump_outputs and rank == 0:                 # before the repeat pass below trains on
         dump_outputs(a.dump_outputs, state.get("last"), opt.bucket, student)
     timed_events, ops.CONV_TIMING = (ops.CONV_TIMING or []), None
-    # the same K steps once more, timed the same way (barrier + synchronize on both sides), WITHOUT the per-launch HIP events of the
-    # roofline bookkeeping: reported as `repeat` (never as `value`) - two figures that agree say the timed region was undisturbed
-    fence()
-    t0r = time.perf_counter()
-    it = run(a.steps, it)
-    fence()
-    dt_rep = time.perf_counter() - t0r
-    if world > 1:
-        tr = torch.tensor([dt_rep], device=dev, dtype=torch.float64)
-        dist.all_reduce(tr, op=dist.ReduceOp.MAX)
-        dt_rep = float(tr.item())
-    # host cost of ONE episode's enqueue on an idle queue (nothing to wait for): what the Python / launch side needs per episode
-    # when it is not throttled by a full launch queue
-    host_idle = 0.0
-    for _ in range(4):
+    # from here on, everything the headline does not need runs with --full only
+    if a.full:
+        # the same K steps once more, timed the same way (barrier + synchronize on both sides), WITHOUT the per-launch HIP events of the
+        # roofline bookkeeping: reported as `repeat` (never as `value`) - two figures that agree say the timed region was undisturbed
         fence()
-        th = time.perf_counter()
-        it = run(every if interval_mode else 1, it)
-        host_idle += (time.perf_counter() - th) / (every if interval_mode else 1)
-    fence()
-    host_idle /= 4
+        t0r = time.perf_counter()
+        it = run(a.steps, it)
+        fence()
+        dt_rep = time.perf_counter() - t0r
+        if world > 1:
+            tr = torch.tensor([dt_rep], device=dev, dtype=torch.float64)
+            dist.all_reduce(tr, op=dist.ReduceOp.MAX)
+            dt_rep = float(tr.item())
+        # host cost of ONE episode's enqueue on an idle queue (nothing to wait for): what the Python / launch side needs per episode
+        # when it is not throttled by a full launch queue
+        host_idle = 0.0
+        for _ in range(4):
+            fence()
+            th = time.perf_counter()
+            it = run(every if interval_mode else 1, it)
+            host_idle += (time.perf_counter() - th) / (every if interval_mode else 1)
+        fence()
+        host_idle /= 4
     ar_events, PAR.ALLREDUCE_TIMING = PAR.ALLREDUCE_TIMING, None
     dist_info = {"backend": None, "world": world, "devices": [torch.cuda.get_device_name(dev)], "allreduce_ms_per_optimizer_step": None,
                  "optimizer_steps_in_timed_region": opt_steps_timed, "allreduce_bucket_bytes": opt.bucket.numel * 4}
@@ -393,21 +401,6 @@ def main():
             f[3] += nbytes
         return fam
 
-    timing = timed_events if a.serial else roofline_pass()
-
-    # roofline of the dominant kernel family (implicit-GEMM conv fwd + dgrad, one template): algorithmic FLOPs / HIP-event time
-    fam = families(timing)
-    if a.layer_table and rank == 0:      # per distinct (kernel family, FLOPs, bytes) launch shape: where the conv time goes
-        shp = {}
-        for name, flops, e0, e1, nbytes in timing:
-            g = shp.setdefault((name, flops, nbytes), [0.0, 0])
-            g[0] += e0.elapsed_time(e1) * 1e-3
-            g[1] += 1
-        tot = sum(g[0] for g in shp.values())
-        print("# kernel family | GFLOP/launch | MB/launch | launches | avg us | TFLOP/s | share of conv time", file=sys.stderr)
-        for (name, flops, nbytes), (t, n) in sorted(shp.items(), key=lambda kv: -kv[1][0]):
-            print("%-18s %7.2f %7.1f %4d %8.1f %6.1f %5.1f%%" % (name, flops / 1e9, nbytes / 1e6, n, t / n * 1e6, flops * n / t / 1e12,
-                                                           100 * t / tot), file=sys.stderr)
     # Forward + data-gradient convolutions run on two kernel families: conv_patch_x3_kernel (same-size 3x3 convolutions of the
     # bf16-plane modes, conv_patch.h) and the im2col-gather kernels (stride-2 / 1x1 / stem; every convolution in f32native).
     # The roofline is that of whichever takes more time; the other one is reported beside it.
@@ -417,9 +410,6 @@ def main():
         pk, gk = fm.get("conv_patch_kernel", ZERO), fm.get("conv_gemm_kernel", ZERO)
         patch_dominant = pk[2] > 0 and pk[1] >= gk[1]
         return (pk, gk, True) if patch_dominant else (gk, pk, False)
-    cg, cg_other, patch_dom = conv_families(fam)
-    wg = fam.get("conv_wgrad_kernel", ZERO)
-    achieved = cg[0] / cg[1] / 1e12
     # dense MFMA peaks (MI355X_MICROARCH.md); the 3xbf16 arithmetic issues 6 bf16 MFMA flops per algorithmic fp32 flop
     PEAK = {"f32": 2500.0 / 3, "f32x3": 2500.0 / 6, "f32native": PEAK_FP32_MFMA_TFLOPS, "bf16": 2500.0, "bf16conv": 2500.0}
     ARITH = {"f32": "v_mfma_f32_16x16x32_f16 x3 per fp32 product, two fp16 planes per operand (h0 + h1 = x 2^s to 2^-23, 2^s from the tensor's "
@@ -435,29 +425,63 @@ def main():
                     "conv_patch16_x3_kernel" if mode == "f32x3" else "conv_patch_x3_kernel") + \
                 " (3x3 conv fwd + dgrad from an LDS-resident input patch; stride-2 launches as parity classes): " + ARITH[mode]
         return ("conv_gemm_kernel" if mode == "f32native" else "conv_gemm_x3_kernel") + " (implicit-GEMM conv fwd + dgrad): " + ARITH[mode]
-    KERNEL = {a.dtype: kernel_name(a.dtype, patch_dom)}
-    PMC_KEY = ("conv_patch16_x3_kernel+conv_patch_x3_kernel" if a.dtype == "f32" else "conv_patch16_x3_kernel" if a.dtype == "f32x3" else "conv_patch_x3_kernel") if patch_dom else ("conv_gemm_kernel" if a.dtype == "f32native" else "conv_gemm_x3_kernel")
-    peak = PEAK[a.dtype]
-    # HBM-side traffic of the same kernel family: rocprofv3 PMC passes (FETCH_SIZE and WRITE_SIZE collected separately,
-    # FETCH_SIZE doubled as MI355X_MICROARCH.md prescribes for 16-B/lane reads on gfx950) of `bench.py --serial`,
-    # committed under profiles/ — counters cannot be read from inside this process.
-    # The file records the hash of the kernel sources it was measured on; a number measured on other kernels is not reported.
-    traffic, traffic_note = None, "no PMC file"
-    import glob
-    tfiles = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_hbm_traffic.json")))
-    if tfiles:
-        tj = json.load(open(tfiles[-1]))
-        if a.dtype != "f32":
-            traffic_note = "%s holds the PMC passes of the headline arithmetic only" % os.path.relpath(tfiles[-1], ROOT)
-        elif tj.get("kernel_src_hash") == kernel_source_hash():
-            traffic = tj.get(PMC_KEY, {}).get("traffic_bytes_per_launch")
-            traffic_note = "rocprofv3 FETCH_SIZE*2 + WRITE_SIZE per launch of %s, %s" % (PMC_KEY, os.path.relpath(tfiles[-1], ROOT))
-        else:
-            traffic_note = "%s was measured on other kernel sources (hash %s, now %s): not reported" % (
-                os.path.relpath(tfiles[-1], ROOT), tj.get("kernel_src_hash"), kernel_source_hash())
-            print("bench.py: " + traffic_note, file=sys.stderr)
+
+    # the per-kernel figures need per-launch records of serialized episodes: the timed region itself with --serial, else a pass of
+    # their own (--full, or --layer-table alone); a plain run reports only what its timed region recorded
+    timing = timed_events if a.serial else roofline_pass() if a.full or a.layer_table else None
+    roofline = {}
+    if timing is not None:
+        # roofline of the dominant kernel family (implicit-GEMM conv fwd + dgrad, one template): algorithmic FLOPs / HIP-event time
+        fam = families(timing)
+        if a.layer_table and rank == 0:      # per distinct (kernel family, FLOPs, bytes) launch shape: where the conv time goes
+            shp = {}
+            for name, flops, e0, e1, nbytes in timing:
+                g = shp.setdefault((name, flops, nbytes), [0.0, 0])
+                g[0] += e0.elapsed_time(e1) * 1e-3
+                g[1] += 1
+            tot = sum(g[0] for g in shp.values())
+            print("# kernel family | GFLOP/launch | MB/launch | launches | avg us | TFLOP/s | share of conv time", file=sys.stderr)
+            for (name, flops, nbytes), (t, n) in sorted(shp.items(), key=lambda kv: -kv[1][0]):
+                print("%-18s %7.2f %7.1f %4d %8.1f %6.1f %5.1f%%" % (name, flops / 1e9, nbytes / 1e6, n, t / n * 1e6, flops * n / t / 1e12,
+                                                               100 * t / tot), file=sys.stderr)
+        cg, cg_other, patch_dom = conv_families(fam)
+        wg = fam.get("conv_wgrad_kernel", ZERO)
+        achieved = cg[0] / cg[1] / 1e12
+        PMC_KEY = ("conv_patch16_x3_kernel+conv_patch_x3_kernel" if a.dtype == "f32" else "conv_patch16_x3_kernel" if a.dtype == "f32x3" else "conv_patch_x3_kernel") if patch_dom else ("conv_gemm_kernel" if a.dtype == "f32native" else "conv_gemm_x3_kernel")
+        peak = PEAK[a.dtype]
+        # HBM-side traffic of the same kernel family: rocprofv3 PMC passes (FETCH_SIZE and WRITE_SIZE collected separately,
+        # FETCH_SIZE doubled, as gfx950 counts the 128-B requests of 16-B/lane reads as 64 B) of `bench.py --serial`,
+        # committed under profiles/ — counters cannot be read from inside this process.
+        # The file records the hash of the kernel sources it was measured on; a number measured on other kernels is not reported.
+        traffic, traffic_note = None, "no PMC file"
+        import glob
+        tfiles = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_hbm_traffic.json")))
+        if tfiles:
+            tj = json.load(open(tfiles[-1]))
+            if a.dtype != "f32":
+                traffic_note = "%s holds the PMC passes of the headline arithmetic only" % os.path.relpath(tfiles[-1], ROOT)
+            elif tj.get("kernel_src_hash") == kernel_source_hash():
+                traffic = tj.get(PMC_KEY, {}).get("traffic_bytes_per_launch")
+                traffic_note = "rocprofv3 FETCH_SIZE*2 + WRITE_SIZE per launch of %s, %s" % (PMC_KEY, os.path.relpath(tfiles[-1], ROOT))
+            else:
+                traffic_note = "%s was measured on other kernel sources (hash %s, now %s): not reported" % (
+                    os.path.relpath(tfiles[-1], ROOT), tj.get("kernel_src_hash"), kernel_source_hash())
+                print("bench.py: " + traffic_note, file=sys.stderr)
+        roofline = {"bound": "mfma", "kernel": kernel_name(a.dtype, patch_dom),
+                    "achieved": achieved, "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak,
+                    "traffic": traffic, "traffic_unit": "bytes per launch", "traffic_note": traffic_note,
+                    "kernel_src_hash": kernel_source_hash(),
+                    "algorithmic_bytes_per_launch": cg[3] / max(cg[2], 1),
+                    "launches": cg[2], "avg_launch_ms": cg[1] / max(cg[2], 1) * 1e3,
+                    "other_conv_family": {"kernel": kernel_name(a.dtype, not patch_dom).split(":")[0], "launches": cg_other[2],
+                                          "tflops": cg_other[0] / cg_other[1] / 1e12, "avg_launch_ms": cg_other[1] / max(cg_other[2], 1) * 1e3},
+                    "wgrad_kernel_tflops": wg[0] / wg[1] / 1e12, "wgrad_avg_launch_ms": wg[1] / max(wg[2], 1) * 1e3,
+                    "measured_on": "timed region (--serial)" if a.serial else "%d extra serialized episodes after the timed region" % a.roofline_episodes}
     frames = 8 * 5 * (a.shot + cfg.query_per_class)
     step_tflop = 3 * FWD_GFLOP_PER_FRAME * frames / 1e3
+    roofline.update({"achieved_in_timed_region": achieved_timed,
+                     "timed_region_conv_tflops_per_gpu": conv_flops_timed / dt / 1e12,
+                     "episode_model_tflops": step_tflop * world * a.steps / dt})
     ops.h2_fence_step(wait=True)      # fp32h2: take in the range fence's last verdicts before they are reported
     out = {
         "metric": "episodes/sec (5-way %d-shot, 8x224^2 frames)" % a.shot, "value": world * a.steps / dt, "unit": "episodes/s",
@@ -495,35 +519,19 @@ def main():
                    "frames_per_episode": frames, "img": 224, "tasks_per_batch": cfg.tasks_per_batch, "optimizer": cfg.opt,
                    "episodes_per_optimizer_step_per_rank": every, "parallelism": "episode-parallel dp%d" % world,
                    "trans_dropout": a.dropout, "trunk_calls_overlapped_on_two_streams": not a.serial},
-        "roofline": {"bound": "mfma", "kernel": KERNEL[a.dtype],
-                     "achieved": achieved, "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak,
-                     "traffic": traffic, "traffic_unit": "bytes per launch", "traffic_note": traffic_note,
-                     "kernel_src_hash": kernel_source_hash(),
-                     "algorithmic_bytes_per_launch": cg[3] / max(cg[2], 1),
-                     "launches": cg[2], "avg_launch_ms": cg[1] / max(cg[2], 1) * 1e3,
-                     "other_conv_family": {"kernel": kernel_name(a.dtype, not patch_dom).split(":")[0], "launches": cg_other[2],
-                                           "tflops": cg_other[0] / cg_other[1] / 1e12, "avg_launch_ms": cg_other[1] / max(cg_other[2], 1) * 1e3},
-                     "wgrad_kernel_tflops": wg[0] / wg[1] / 1e12, "wgrad_avg_launch_ms": wg[1] / max(wg[2], 1) * 1e3,
-                     "measured_on": "timed region (--serial)" if a.serial else "%d extra serialized episodes after the timed region" % a.roofline_episodes,
-                     "achieved_in_timed_region": achieved_timed,
-                     "timed_region_conv_tflops_per_gpu": conv_flops_timed / dt / 1e12,
-                     "episode_model_tflops": step_tflop * world * a.steps / dt},
+        "roofline": roofline,
         "distributed": dist_info,
-        # host side: time to ENQUEUE one episode on an idle queue (4 samples after the timed region; an optimizer step may fall on one
-        # of them), and the time the Python loop spent enqueueing the timed region - there the host is throttled by the full launch
-        # queue whenever the GPU is the bottleneck
-        "repeat": {"value": world * a.steps / dt_rep, "unit": "episodes/s", "steps": a.steps,
-                   "what": "the timed K steps run a second time right after the timed region, without per-launch timing events"},
         "device_mallocs_in_timed_region": mallocs_timed,
         "allocator_priming_episodes": primed if not interval_mode else 0,
         # HBM held by the caching allocator against what the tensors need at their peak: the gap is the allocator's per-stream pools (a block
         # belongs to the stream it was allocated on; five streams x the 6 GB of activations a trunk call saves, two or three episodes in flight)
         "hbm_GB": ({"reserved": round(torch.cuda.memory_stats(dev).get("reserved_bytes.all.peak", 0) / 2 ** 30, 1),
                     "allocated_peak": round(torch.cuda.memory_stats(dev).get("allocated_bytes.all.peak", 0) / 2 ** 30, 1)} if dev.type == "cuda" else None),
-        "host_enqueue_ms_per_episode": host_idle * 1e3,
+        # host side: the time the Python loop spent enqueueing the timed region - the host is throttled by the full launch queue there
+        # whenever the GPU is the bottleneck (host_enqueue_ms_per_episode below, --full: the same on an idle queue)
         "host_loop_ms_per_episode_in_timed_region": t_enq / a.steps * 1e3,
         "episode_pipelining": bool(use_pipe),
-        # after every timed / repeated / probe episode and optimizer step of this process (ReLU(NaN) = 0 keeps a loss finite on NaN weights)
+        # after every episode and optimizer step this process has run so far (ReLU(NaN) = 0 keeps a loss finite on NaN weights)
         "weights_finite": bool(torch.isfinite(opt.bucket.flat).all()),
         # the range fence of the two-plane arithmetic (ops.h2_fence_step after every backward pass): launches that fell back to the three-plane
         # form because their tensor was flagged, and the flagged tensors ("y" | "a" | "d" | "p", BatchNorm) - expected 0 / none on this benchmark
@@ -532,13 +540,18 @@ def main():
         "hipgraph": {"enabled": bool(use_graph), "replays": runners[a.dtype].replays if use_graph else 0,
                      "eager_episodes": runners[a.dtype].eager if use_graph else None, "graphs": len(runners[a.dtype].graphs) if use_graph else 0},
     }
+    if a.full:
+        out["repeat"] = {"value": world * a.steps / dt_rep, "unit": "episodes/s", "steps": a.steps,
+                         "what": "the timed K steps run a second time right after the timed region, without per-launch timing events"}
+        # time to ENQUEUE one episode on an idle queue (4 samples after the timed region; an optimizer step may fall on one of them)
+        out["host_enqueue_ms_per_episode"] = host_idle * 1e3
     if a.emulate_world > 0:
         out["emulated_world"] = {"world": a.emulate_world, "episodes_per_optimizer_step": every,
                                  "note": "per-rank cadence of a %d-rank run rehearsed on ONE GPU (optimizer step + weight re-pack every %d episodes, "
                                          "no collective): value x %d would be the job's rate at perfect scaling" % (a.emulate_world, every, a.emulate_world)}
     if a.stream_inputs:
         out["stream_inputs"] = stream_inputs_pass(a, cfg, dev, run, state, fence, TL)
-    if world == 1 and a.dtype == "f32" and not a.no_other_modes:
+    if a.full and world == 1 and a.dtype == "f32" and not a.no_other_modes:
         # the same job in the two other arithmetic modes of the convolutions, for the record (never part of `value`):
         # short timed regions right here, same process, same resident episodes, each with its own per-kernel roofline pass
         other = {}
@@ -576,7 +589,7 @@ def main():
                                          "algorithmic_bytes_per_episode": ALG_BYTES_PER_EPISODE,
                                          "note": "bf16 activations: 3 x 12.9 MB per frame (SURVEY 8d); whole-job average, not one kernel"}
         out["other_modes"] = other
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(a.shot, a.cpu_episodes)
     if rank == 0:
         print(json.dumps(out), flush=True)

@@ -584,6 +584,33 @@ def test_bench_world2_gloo_rehearsal_on_one_gpu(dev):
     assert line["weights_finite"] and line["value"] > 0
 
 
+def test_bench_plain_and_full_lines(dev):
+    """a plain `bench.py` run measures the headline alone: set-up, priming, warm-up, the timed steps, the line - no repeat of the timed
+    steps, host-enqueue probe, serialized roofline pass, other arithmetic modes or CPU baseline; `--full` adds every one of them."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    extra = {"repeat", "host_enqueue_ms_per_episode", "other_modes", "cpu_baseline"}
+
+    def bench_line(*args):
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "4", "--warmup", "1", "--prime", "16", *args],
+                             capture_output=True, text=True, timeout=600, cwd=root)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, "ONE JSON line"
+        return json.loads(lines[0])
+    plain = bench_line()
+    assert plain["value"] > 0 and plain["ms_per_step"] > 0 and plain["dtype"] == "f32" and plain["unit"] == "episodes/s"
+    assert plain["higher_is_better"] and plain["weights_finite"] and not extra & set(plain)
+    assert set(plain["roofline"]) == {"achieved_in_timed_region", "timed_region_conv_tflops_per_gpu", "episode_model_tflops"}
+    full = bench_line("--full", "--cpu-episodes", "1")
+    assert extra <= set(full) and set(full["other_modes"]) == {"f32x3", "f32native", "bf16"}
+    assert full["repeat"]["value"] > 0 and full["host_enqueue_ms_per_episode"] > 0 and full["cpu_baseline"]["value"] > 0
+    assert full["roofline"]["launches"] > 0 and full["roofline"]["achieved"] > 0 and "achieved_in_timed_region" in full["roofline"]
+
+
 def test_train_cli_synthetic_and_clip_directory(dev, tmp_path):
     """python -m litemkd_amd.train (reference flags, options.py:7-76): a few iterations on synthetic episodes with a checkpoint in the
     reference's format, then on a directory of decoded uint8 clips through the GPU frame transform (video_reader.py:398-485 sampling)"""

@@ -7,6 +7,6 @@ COMMON="--steps 32 --warmup 5 --no-cpu-baseline --no-other-modes --roofline-epis
 val() { tail -1 | python3 -c 'import sys,json; d=json.loads(sys.stdin.read()); print(d["dtype"], round(d["value"],2), "episodes/s", "host", round(d.get("host_enqueue_ms_per_episode",-1),2))'; }
 for i in $(seq $R); do
   echo "B prev       $(cd .ab_prev && python bench.py $COMMON 2>/dev/null | val)"
-  echo "A new eager  $(python bench.py $COMMON --no-graph 2>/dev/null | val)"
-  echo "A new graph  $(python bench.py $COMMON 2>/dev/null | val)"
+  echo "A new eager  $(python bench.py $COMMON --full --no-graph 2>/dev/null | val)"
+  echo "A new graph  $(python bench.py $COMMON --full 2>/dev/null | val)"
 done

@@ -4,7 +4,7 @@
 # hipGraph, pipelining), inference, layer tables, the numerical and ablation probes, host-side probes.  Everything lands in gpurun_out/final_<tag>/.
 # (6 s between processes: a process started while the previous one's memory is still being released runs slow - DESIGN 8.8)
 tag=${1:-r03}; part=${2:-all}; out=gpurun_out/final_$tag; mkdir -p $out      # part: 1 | 2 | 3 | all (a gpurun call is capped at 20 minutes)
-B="python bench.py"
+B="python bench.py --full"
 [ "$part" = all -o "$part" = 1 ] && { sleep 6; $B --steps 20 --warmup 5 --stream-inputs --layer-table > $out/bench.json 2> $out/layer_table.txt; echo "bench $?"; }
 [ "$part" = all -o "$part" = 1 ] && { sleep 6; $B --steps 32 --warmup 5 --no-cpu-baseline --no-other-modes --dtype bf16 --layer-table > $out/bench_bf16.json 2> $out/layer_table_bf16.txt; echo "bf16 $?"; }
 [ "$part" = all -o "$part" = 1 ] && { sleep 6; $B --steps 32 --warmup 5 --no-cpu-baseline --no-other-modes --dtype f32x3 --layer-table > $out/bench_f32x3.json 2> $out/layer_table_f32x3.txt; echo "f32x3 $?"; }
