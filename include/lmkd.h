@@ -208,6 +208,31 @@ int lmkd_resize_pass_u8(const unsigned char* src, unsigned char* dst, const int*
 int lmkd_frames_resize_crop_nhwc4(const unsigned char* src, float* dst, const int* bounds_h, const int* coeffs_h, int ksize_h,
                                   const int* bounds_v, const int* coeffs_v, int ksize_v, const int* crop_y, const int* crop_x,
                                   const int* flip, int F, int Hs, int Ws, int Hr, int Wr, int H, int W, int frames_per_video, void* stream);
+/* ---- baseline JPEG frames (video_reader.py:334-343 read_single_image = PIL.Image.open(f).load(): libjpeg-turbo defaults), csrc/jpeg.hip.
+ * The GPU decodes SOF0 Huffman 8-bit YCbCr (ids 1,2,3 or JFIF, no Adobe marker) in 4:4:4 / 4:2:2 / 4:2:0 with one interleaved scan and
+ * optional restart intervals, bit-identical to PIL; everything else is "unsupported" (the caller decodes it with PIL).
+ * lmkd_jpeg_plan (HOST, no device work): image i = data[offsets[i] .. offsets[i+1]) of one host buffer; writes n descriptors of
+ * lmkd_jpeg_desc_bytes() into `descs`, the derived tables into `pool` (pool_cap bytes; lmkd_jpeg_pool_bytes(n) always suffices; identical
+ * tables are stored once), info[5 i ..] = verdict (0 decoded on the GPU, 1 unsupported, 2 malformed), reason (lmkd_jpeg_reason), height,
+ * width, byte offset of the image's uint8 [H][W][3] in the output (images packed in order, malformed ones take no room);
+ * totals = pool bytes used, coefficient blocks, output bytes, most blocks of one image, most pixels of one image.  Offsets in the
+ * descriptors are relative to `data`: upload data, descs and the used pool unchanged. */
+long lmkd_jpeg_desc_bytes(void);
+long lmkd_jpeg_pool_bytes(int n);
+const char* lmkd_jpeg_reason(int reason);
+int lmkd_jpeg_plan(const unsigned char* data, const long long* offsets, int n, void* descs, void* pool, long pool_cap, long long* info,
+                   long long* totals);
+/* three launches (entropy decode, one wave per image; dequantise + islow IDCT; fancy upsampling + YCbCr -> RGB) on `stream`:
+ * data (4-byte aligned), descs, pool (16-byte aligned) = the device copies of the plan's buffers; coef: int16 [totals[1]][64] (16-byte
+ * aligned), planes: uint8 [totals[1]][64] scratch; out: the output bytes; status[i] (device int) = 0, or the error that stopped image i
+ * (1 bad Huffman code, 2 coefficient index past 63, 3 data ends early, 4 restart marker out of sequence, 5 data left at the end of the
+ * scan, 6 data does not fit the decoder's window); unsupported / malformed images are left untouched (status 0).
+ * max_blocks / max_pixels = totals[3] / totals[4]. */
+int lmkd_jpeg_decode(const unsigned char* data, const void* descs, const void* pool, int n, short* coef, unsigned char* planes,
+                     unsigned char* out, int* status, long long max_blocks, long long max_pixels, void* stream);
+/* the same routines on the CPU, every pointer HOST memory (the tests' reference; not on the training path) */
+int lmkd_jpeg_decode_host(const unsigned char* data, const void* descs, const void* pool, int n, short* coef, unsigned char* planes,
+                          unsigned char* out, int* status);
 /* amax_words (nullable; mode 4): also fold max |y| into the slots of ONE frame segment at this address (lmkd_amax_words() / 2 words) */
 int lmkd_nchw3_to_nhwc4(const float* x_nchw, float* y_nhwc4, int N, int H, int W, void* stream, void* amax_words);
 /* Ticket words: the single-launch column reductions (lmkd_bn_finalize, lmkd_bn_backward, lmkd_colsum) elect their finishing workgroup

@@ -5,8 +5,9 @@ convolution epilogue), print the per-task accuracy and return mean accuracy x100
 
     python -m litemkd_amd.evaluate --test_model student --test_model_path model_save/<ckpt>.pt --num_test_tasks 100
 
-Data: any iterable of task dicts with the VideoDataset contract (video_reader.py:474-485); without one, synthetic test episodes
-(trainloop.SyntheticEpisodes(train=False): 1 query per class, as `query_per_class_test`)."""
+Data: any iterable of task dicts with the VideoDataset contract (video_reader.py:474-485); on the command line --rgb_path (with
+--traintestlist / --split) tests on the test split of the reference's JPEG frame tree (train.JpegFrameEpisodes); without either,
+synthetic test episodes (trainloop.SyntheticEpisodes(train=False): 1 query per class, as `query_per_class_test`)."""
 import numpy as np
 import torch
 
@@ -76,9 +77,24 @@ def main(argv=None):
         ap.add_argument("--" + k, default=getattr(base, k))
     for k in ("num_test_tasks", "way", "shot", "query_per_class_test", "seq_len", "img_size"):
         ap.add_argument("--" + k, type=int, default=getattr(base, k))
+    # the reference's data tree (train.py --rgb_path): the test split's videos, frames decoded on the GPU
+    ap.add_argument("--rgb_path", default=None, help="<rgb_path>/<class>/<video>/<frame>.jpg or an uncompressed .zip of it")
+    ap.add_argument("--traintestlist", default=None, help="directory of the split lists {train,test}list<split>.txt")
+    ap.add_argument("--teacher_path", default=None, help="teacher features <teacher_path>/<class>/<video>/<file>.npy (--test_model teacher)")
+    ap.add_argument("--split", type=int, default=getattr(base, "split", 3))
+    ap.add_argument("--seed", type=int, default=0)
     a = ap.parse_args(argv)
-    args = default_args(**vars(a))
-    print(Evaluator(args).test())
+    kw = {k: v for k, v in vars(a).items() if k not in ("rgb_path", "traintestlist", "teacher_path", "seed")}
+    args = default_args(**kw)
+    loader = None
+    if a.rgb_path:
+        import random
+        from .train import JpegFrameEpisodes
+        random.seed(a.seed)
+        loader = JpegFrameEpisodes(args, a.rgb_path, a.traintestlist, a.teacher_path, split=a.split, device=args.device, train=False)
+    result = Evaluator(args, video_loader=loader).test()
+    print(result)
+    return result
 
 
 if __name__ == "__main__":

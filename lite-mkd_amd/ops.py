@@ -1547,6 +1547,225 @@ def frames_resize_crop_nhwc4(frames_u8, resize, crop_y, crop_x, flip, size, fram
     return out
 
 
+# ------------------------------------------------------------------------------------------
+# JPEG frames (csrc/jpeg.hip): the decode step of the reference's input chain (video_reader.py:334-343 read_single_image,
+# PIL.Image.open(f).load()) on the GPU, bit-identical to PIL
+# ------------------------------------------------------------------------------------------
+JPEG_SUPPORTED, JPEG_UNSUPPORTED, JPEG_MALFORMED = 0, 1, 2
+JPEG_DEVICE_ERRORS = {1: "bad Huffman code", 2: "coefficient index past 63", 3: "entropy-coded data ends early",
+                      4: "restart marker out of sequence", 5: "data left over at the end of the scan",
+                      6: "entropy-coded data does not fit the decoder's window"}
+_JPEG_STATS = {"images": 0, "gpu": 0, "fallback": 0}
+_JPEG_SCRATCH = {}      # (device index, stream) -> {"in", "coef", "planes"}: grown on demand, reused in stream order
+
+
+def jpeg_stats(reset=False):
+    """images handled by jpeg_decode so far: {"images", "gpu", "fallback"} (fallback: decoded on the host with PIL because the plan
+    marked them unsupported)"""
+    out = dict(_JPEG_STATS)
+    if reset:
+        for k in _JPEG_STATS:
+            _JPEG_STATS[k] = 0
+    return out
+
+
+def _align(n, a=256):
+    return (int(n) + a - 1) // a * a
+
+
+class PinnedRing:
+    """a ring of pinned host buffers for JpegPlan: a slot is reused once the H2D copy that read it has passed (the event decode()
+    records after it); pinning a fresh buffer per episode costs milliseconds of hipHostMalloc"""
+
+    def __init__(self, n=6):
+        self.slots = [None] * max(2, int(n))
+        self.i = 0
+
+    def get(self, nbytes):
+        k = self.i % len(self.slots)
+        self.i += 1
+        s = self.slots[k]
+        if s is not None and s["event"] is not None:
+            s["event"].synchronize()
+            s["event"] = None
+        if s is None or s["buf"].numel() < nbytes:
+            s = self.slots[k] = {"buf": torch.empty(_align(nbytes * 5 // 4, 1 << 20), dtype=torch.uint8).pin_memory(), "event": None}
+        return s
+
+
+def _pil_decode(data, name):
+    """the reference's own decoder for the images the plan marks unsupported (progressive, arithmetic, grayscale, ...)"""
+    import io
+    import numpy as np
+    from PIL import Image
+    with Image.open(io.BytesIO(data)) as im:
+        im.load()
+        if im.mode != "RGB":
+            raise ValueError("JPEG %s: PIL decodes it as mode %s, the frame transform takes RGB" % (name, im.mode))
+        return np.array(im)
+
+
+class JpegPlan:
+    """The host half of a batch decode (lmkd_jpeg_plan): the images' bytes, their descriptors and the table pool in ONE host buffer laid
+    out [descriptors | data | pool] (pinned when a GPU is present: one H2D copy of the used prefix), the verdict per image, and the PIL
+    decode of the images the plan marks unsupported (done here, on the thread that builds the plan - a loader's prefetch thread).
+
+    blobs: list of bytes / uint8 tensors, or one packed uint8 tensor with `offsets` (n + 1 byte offsets).  names: optional per-image names
+    for the error messages (a loader passes the frame files).  fallback=False skips the PIL decode (the plan's verdicts alone)."""
+
+    def __init__(self, blobs, offsets=None, names=None, ring=None, pin=None, fallback=True):
+        import numpy as np
+        if offsets is not None:
+            packed = blobs.reshape(-1) if torch.is_tensor(blobs) else torch.frombuffer(bytearray(blobs), dtype=torch.uint8)
+            offs = [int(o) for o in offsets]
+            blobs = [packed[offs[i]:offs[i + 1]].numpy() for i in range(len(offs) - 1)]
+        else:
+            blobs = [b.cpu().reshape(-1).numpy() if torch.is_tensor(b) else np.frombuffer(b, dtype=np.uint8) for b in blobs]
+        n = len(blobs)
+        if n == 0:
+            raise ValueError("jpeg_decode: no images")
+        self.n, self.names = n, names
+        sizes = [len(b) for b in blobs]
+        dbytes = lib().value("lmkd_jpeg_desc_bytes")
+        self.data_off = _align(n * dbytes)
+        self.pool_off = _align(self.data_off + sum(sizes))
+        pool_cap = lib().value("lmkd_jpeg_pool_bytes", n)
+        need = self.pool_off + pool_cap
+        pin = torch.cuda.is_available() if pin is None else pin
+        if ring is not None and pin:
+            self.slot = ring.get(need)
+        else:
+            buf = torch.empty(need, dtype=torch.uint8)
+            self.slot = {"buf": buf.pin_memory() if pin else buf, "event": None}
+        self.buf = self.slot["buf"]
+        arr = self.buf.numpy()
+        offs = [0]
+        for b in blobs:
+            p = self.data_off + offs[-1]
+            arr[p:p + len(b)] = b
+            offs.append(offs[-1] + len(b))
+        self.offsets = np.asarray(offs, dtype=np.int64)
+        self.info = np.zeros((n, 5), dtype=np.int64)
+        self.totals = np.zeros(5, dtype=np.int64)
+        base = self.buf.data_ptr()
+        lib().call("lmkd_jpeg_plan", ctypes.c_void_p(base + self.data_off), ctypes.c_void_p(self.offsets.ctypes.data), n, ctypes.c_void_p(base),
+                   ctypes.c_void_p(base + self.pool_off), pool_cap, ctypes.c_void_p(self.info.ctypes.data), ctypes.c_void_p(self.totals.ctypes.data))
+        self.nbytes = self.pool_off + int(self.totals[0])          # what the device needs
+        self.fallback = {}
+        if fallback and not (self.info[:, 0] == JPEG_MALFORMED).any():
+            for i in np.nonzero(self.info[:, 0] == JPEG_UNSUPPORTED)[0]:
+                i = int(i)
+                img = _pil_decode(bytes(arr[self.data_off + offs[i]:self.data_off + offs[i + 1]]), self.name(i))
+                if img.shape[:2] != self.shape(i):
+                    raise ValueError("JPEG %s: PIL decodes %s, the header says %s" % (self.name(i), img.shape[:2], self.shape(i)))
+                t = torch.from_numpy(img)
+                self.fallback[i] = t.pin_memory() if pin else t
+
+    def name(self, i):
+        return "image %d%s" % (i, " (%s)" % self.names[i] if self.names is not None else "")
+
+    def verdicts(self):
+        """[(verdict, reason text)] per image"""
+        return [(int(v), lib().value("lmkd_jpeg_reason", int(r)).decode()) for v, r in self.info[:, :2]]
+
+    def shape(self, i):
+        return int(self.info[i, 2]), int(self.info[i, 3])
+
+    def shapes(self):
+        return [self.shape(i) for i in range(self.n)]
+
+    def check(self):
+        """ValueError naming the first image whose header or table the plan found malformed"""
+        for i in range(self.n):
+            if self.info[i, 0] == JPEG_MALFORMED:
+                raise ValueError("JPEG %s is malformed: %s" % (self.name(i), lib().value("lmkd_jpeg_reason", int(self.info[i, 1])).decode()))
+
+    def raise_on_status(self, status):
+        """ValueError naming the first image the GPU decoder stopped (status: the host copy of decode()'s status words)"""
+        for i, s in enumerate(status.tolist() if torch.is_tensor(status) else list(status)):
+            if s:
+                raise ValueError("JPEG %s is malformed: %s" % (self.name(i), JPEG_DEVICE_ERRORS.get(int(s), "error %d" % s)))
+
+    def decode(self, out=None, check=True, device=None):
+        """the three decode launches on the current stream (+ the H2D copy, + the copies of the PIL-decoded fallback images) -> (frames,
+        status): frames = uint8 [F, H, W, 3] when every image has the same size (or `out`, any contiguous uint8 tensor of the total size),
+        else a list of [H, W, 3] views; status = int32 device tensor, 0 or the error that stopped the image.  check: read the status words
+        (a synchronisation) and raise ValueError for a malformed image; a streamed loader passes False and reads them later."""
+        self.check()
+        dev = torch.device(device) if device is not None else (out.device if out is not None else torch.device("cuda", torch.cuda.current_device()))
+        stream = torch.cuda.current_stream(dev)
+        total = int(self.totals[2])
+        shapes = self.shapes()
+        uniform = len(set(shapes)) == 1
+        if out is None:
+            out = torch.empty((self.n,) + shapes[0] + (3,) if uniform else (total,), dtype=torch.uint8, device=dev)
+        elif out.dtype != torch.uint8 or not out.is_contiguous() or not out.is_cuda or out.numel() != total:
+            raise RuntimeError("jpeg_decode: `out` must be a contiguous uint8 device tensor of %d bytes" % total)
+        flat = out.view(-1)
+        key = (device_index(dev), stream.cuda_stream)
+        sc = _JPEG_SCRATCH.get(key)
+        blocks = int(self.totals[1])
+        if sc is None or sc["in"].numel() < self.nbytes or sc["coef"].numel() < blocks * 64:
+            nb = max(self.nbytes, sc["in"].numel() if sc else 0)
+            nk = max(blocks * 64, sc["coef"].numel() if sc else 0, 64)
+            sc = _JPEG_SCRATCH[key] = {"in": torch.empty(_align(nb * 5 // 4, 1 << 20), dtype=torch.uint8, device=dev),
+                                       "coef": torch.empty(_align(nk * 5 // 4), dtype=torch.int16, device=dev),
+                                       "planes": torch.empty(_align(nk * 5 // 4), dtype=torch.uint8, device=dev)}
+        dbuf = sc["in"]
+        dbuf[:self.nbytes].copy_(self.buf[:self.nbytes], non_blocking=True)
+        if self.buf.is_pinned():
+            ev = torch.cuda.Event()
+            ev.record(stream)
+            self.slot["event"] = ev                                 # the host buffer may be reused once the copy has run
+        status = torch.empty(self.n, dtype=torch.int32, device=dev)
+        base = dbuf.data_ptr()
+        lib().call("lmkd_jpeg_decode", ctypes.c_void_p(base + self.data_off), ctypes.c_void_p(base), ctypes.c_void_p(base + self.pool_off), self.n,
+                   _p(sc["coef"]), _p(sc["planes"]), _p(flat), _p(status), int(self.totals[3]), int(self.totals[4]), ctypes.c_void_p(stream.cuda_stream))
+        for i, img in self.fallback.items():
+            o = int(self.info[i, 4])
+            flat[o:o + img.numel()].copy_(img.view(-1), non_blocking=True)
+        _JPEG_STATS["images"] += self.n
+        _JPEG_STATS["fallback"] += len(self.fallback)
+        _JPEG_STATS["gpu"] += self.n - len(self.fallback)
+        if check:
+            self.raise_on_status(status.cpu())
+        if out.dim() == 4 or not uniform:
+            frames = out if out.dim() == 4 else [flat[int(self.info[i, 4]):int(self.info[i, 4]) + h * w * 3].view(h, w, 3)
+                                                 for i, (h, w) in enumerate(shapes)]
+        else:
+            frames = flat.view((self.n,) + shapes[0] + (3,))
+        return frames, status
+
+
+def jpeg_decode(blobs, out=None, offsets=None, names=None, check=True):
+    """decode a batch of JPEG images on the GPU (current stream) -> (frames, status): see JpegPlan.decode.  blobs: list of bytes / uint8
+    tensors, one packed uint8 tensor with `offsets`, or a JpegPlan built beforehand (a loader's prefetch thread).  Images the plan marks
+    unsupported are decoded with PIL (counted in jpeg_stats()); a malformed image raises ValueError naming its index."""
+    plan = blobs if isinstance(blobs, JpegPlan) else JpegPlan(blobs, offsets=offsets, names=names)
+    return plan.decode(out=out, check=check)
+
+
+def jpeg_decode_host(blobs):
+    """lmkd_jpeg_decode_host: the device routines run on the CPU (the tests' reference) -> (list of uint8 [H, W, 3] numpy arrays,
+    None for images the plan does not decode on the GPU; the plan; status per image)"""
+    import numpy as np
+    plan = JpegPlan(blobs, pin=False)
+    blocks = int(plan.totals[1])
+    coef = np.zeros(max(1, blocks * 64), dtype=np.int16)
+    planes = np.zeros(max(1, blocks * 64), dtype=np.uint8)
+    out = np.zeros(max(1, int(plan.totals[2])), dtype=np.uint8)
+    status = np.zeros(plan.n, dtype=np.int32)
+    base = plan.buf.data_ptr()
+    P = lambda a: ctypes.c_void_p(a.ctypes.data)      # noqa: E731
+    lib().call("lmkd_jpeg_decode_host", ctypes.c_void_p(base + plan.data_off), ctypes.c_void_p(base), ctypes.c_void_p(base + plan.pool_off),
+               plan.n, P(coef), P(planes), P(out), P(status))
+    imgs = []
+    for i, (h, w) in enumerate(plan.shapes()):
+        o = int(plan.info[i, 4])
+        imgs.append(out[o:o + h * w * 3].reshape(h, w, 3).copy() if plan.info[i, 0] == JPEG_SUPPORTED else None)
+    return imgs, plan, status
+
+
 # parallel.EarlyAllReduce: while set, the trunk's forward registers this tensor hook on the input of its last stage - it fires when the
 # backward pass has left that stage (the gradients of the last stage, the heads and the matcher are final)
 GRAD_READY_HOOK = None

@@ -8,18 +8,20 @@ train_wandb.sh):
 Every flag of the reference's parser is accepted under its own name and default (so train_wandb.sh's command line parses unchanged);
 the defaults of the three plugin names are train_wandb.sh's values instead of the parser's (`strm18_student` / `TRX` / `test_teacher`
 are outside this build's scope).  What the reference does around the loop and this build does not: wandb logging (a
-JSON-lines log instead, --log_jsonl), JPEG decoding (episodes come from SyntheticEpisodes or, with --data_dir, from a directory of decoded
-uint8 clips through the GPU frame transform).  One process per GPU: under torchrun every rank runs this script on its own episode stream
+JSON-lines log instead, --log_jsonl).  Episodes come from SyntheticEpisodes, from the reference's own JPEG frame tree (--rgb_path,
+--traintestlist, --teacher_path: JpegFrameEpisodes, decoded on the GPU) or, with --data_dir, from a directory of decoded uint8 clips;
+the frame transform runs on the GPU.  One process per GPU: under torchrun every rank runs this script on its own episode stream
 and the optimizer step all-reduces the gradient bucket (parallel.py).
 
 Extra flags (not in the reference): --dtype, --two_call, --serial (schedule.Schedule), --data_dir / --feature_dir, --log_jsonl,
---seed, --no_save."""
+--seed, --no_save.  --rgb_path / --traintestlist / --teacher_path carry the names of the reference's dataset attributes."""
 import argparse
 import json
 import os
 import random
 import sys
 import time
+import zipfile
 
 import numpy as np
 import torch
@@ -99,6 +101,10 @@ def build_parser():
                    "the default merged + pipelined one (Schedule.bench())")
     p.add_argument("--data_dir", default=None, help="directory of decoded clips: <data_dir>/<class>/<video>.npy, uint8 [T, H, W, 3]")
     p.add_argument("--feature_dir", default=None, help="teacher features: <feature_dir>/<class>/<video>.npy, float [seq_len, 2048] (default: next to the clips, <video>.feature.npy)")
+    p.add_argument("--rgb_path", default=None, help="the reference's frame tree: <rgb_path>/<class>/<video>/<frame>.jpg, or an uncompressed "
+                   ".zip of it (JpegFrameEpisodes: decoded on the GPU); exclusive with --data_dir")
+    p.add_argument("--traintestlist", default=None, help="with --rgb_path: directory of the split lists {train,test}list<split>.txt (--split)")
+    p.add_argument("--teacher_path", default=None, help="with --rgb_path: teacher features <teacher_path>/<class>/<video>/<file>.npy")
     p.add_argument("--log_jsonl", default=None, help="append one JSON line per print_freq iterations (the reference logs to wandb)")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--no_save", action="store_true", help="write no checkpoints")
@@ -142,11 +148,12 @@ class ClipDirectoryEpisodes:
             raise ValueError("%s holds %d classes, the episodes need %d" % (root, len(self.classes), config.way))
         self.tf = GpuFrameTransform(config.img_size, device)
 
-    def _frames(self, clip):
-        n, L = clip.shape[0], self.c.seq_len
+    def _frame_idxs(self, n, train):
+        """get_seq's frame choice (video_reader.py:345-375) for a video of n frames"""
+        L = self.c.seq_len
         if n == L:
-            return clip
-        if self.train:
+            return list(range(n))
+        if train:
             excess_pad = int(min(5, (n - L) / 2))
             if excess_pad < 1:
                 start, end = 0, n - 1
@@ -157,65 +164,232 @@ class ClipDirectoryEpisodes:
             start, end = 1, n - 2
         if end - start < L:
             start, end = 0, n - 1
-        idxs = [int(f) for f in np.linspace(start, end, num=L)]
-        return clip[idxs]
+        return [int(f) for f in np.linspace(start, end, num=L)]
+
+    def _frames(self, clip, train=None):
+        return clip[self._frame_idxs(clip.shape[0], self.train if train is None else train)]
+
+    def _classes(self, train):
+        """{class: [videos]} the draws of a `train` / test episode choose from"""
+        return self.classes
+
+    def _open(self, cname, vid):
+        """-> (handle, frame count) of one video: here the memory-mapped clip"""
+        clip = np.load(os.path.join(self.root, cname, vid + ".npy"), mmap_mode="r")
+        return clip, clip.shape[0]
 
     def _feature(self, cname, vid):
         path = (os.path.join(self.froot, cname, vid + ".npy") if self.froot else os.path.join(self.root, cname, vid + ".feature.npy"))
         return torch.from_numpy(np.load(path)).float()
 
+    def _draw(self, train):
+        """the draws of one episode in the reference's order - classes, videos, each video's frames, the two shuffles - for both
+        episode() and host_episode(), and for JpegFrameEpisodes: -> (support, query) lists of (class, video, handle, frame indices,
+        label).  The per-video flip / crop draws follow (GpuFrameTransform.draw, support videos first)."""
+        c = self.c
+        nq = c.query_per_class if train else c.query_per_class_test
+        classes = self._classes(train)
+        batch_classes = random.sample(list(classes), c.way)
+        sup, tgt = [], []
+        for bl, bc in enumerate(batch_classes):
+            vids = classes[bc]
+            if len(vids) < c.shot + nq:
+                raise ValueError("class %s has %d videos, an episode needs %d" % (bc, len(vids), c.shot + nq))
+            idxs = random.sample(range(len(vids)), c.shot + nq)
+            for j, i in enumerate(idxs):
+                h, n = self._open(bc, vids[i])
+                (sup if j < c.shot else tgt).append((bc, vids[i], h, self._frame_idxs(n, train), bl))
+        random.shuffle(sup)
+        random.shuffle(tgt)
+        return sup, tgt
+
+    @staticmethod
+    def _labels(sup, tgt, way):
+        return {"support_labels": torch.FloatTensor([v[4] for v in sup]), "target_labels": torch.FloatTensor([v[4] for v in tgt]),
+                "real_target_labels": torch.FloatTensor([v[4] for v in tgt]), "batch_class_list": torch.arange(way).float()}
+
     def host_episode(self):
         """the HOST half of episode() for trainloop.StreamedEpisodes (a prefetch thread calls it): the same draws in the same order - classes,
         videos, frames, the two shuffles, then per video flip / crop (support videos first) - but no device work: the decoded frames of all
         videos as ONE uint8 tensor (they must share a resolution: one H2D copy, one resize launch), the crop parameters, the features"""
-        c = self.c
-        nq = c.query_per_class if self.train else c.query_per_class_test
-        batch_classes = random.sample(list(self.classes), c.way)
-        sup, tgt = [], []
-        for bl, bc in enumerate(batch_classes):
-            vids = self.classes[bc]
-            if len(vids) < c.shot + nq:
-                raise ValueError("class %s has %d videos, an episode needs %d" % (bc, len(vids), c.shot + nq))
-            idxs = random.sample(range(len(vids)), c.shot + nq)
-            for j, i in enumerate(idxs):
-                clip = torch.from_numpy(self._frames(np.load(os.path.join(self.root, bc, vids[i] + ".npy"), mmap_mode="r")).copy())
-                (sup if j < c.shot else tgt).append((clip, self._feature(bc, vids[i]), bl))
-        random.shuffle(sup)
-        random.shuffle(tgt)
-        vids = [v[0] for v in sup + tgt]
+        train = self.train                  # read once: an episode is wholly of one mode
+        sup, tgt = self._draw(train)
+        vids = [torch.from_numpy(np.ascontiguousarray(v[2][v[3]])) for v in sup + tgt]
         if len({tuple(v.shape[1:3]) for v in vids}) != 1:
             raise ValueError("StreamedEpisodes needs one frame resolution per episode (got %s): use the loader without --stream_inputs"
                              % sorted({tuple(v.shape[1:3]) for v in vids}))
-        params = [self.tf.draw(v.shape[1], v.shape[2], self.train) for v in vids]
-        return {"frames": torch.cat(vids, 0), "params": params, "features": torch.stack([v[1] for v in sup + tgt]), "ns": len(sup),
-                "support_labels": torch.FloatTensor([v[2] for v in sup]), "target_labels": torch.FloatTensor([v[2] for v in tgt]),
-                "real_target_labels": torch.FloatTensor([v[2] for v in tgt]), "batch_class_list": torch.arange(c.way).float()}
+        params = [self.tf.draw(v.shape[1], v.shape[2], train) for v in vids]
+        d = {"frames": torch.cat(vids, 0), "params": params, "features": torch.stack([self._feature(v[0], v[1]) for v in sup + tgt]),
+             "ns": len(sup)}
+        d.update(self._labels(sup, tgt, self.c.way))
+        return d
+
+    def _task(self, sup_videos, tgt_videos, sup, tgt, train):
+        # one transform call per set: the per-video flip / crop draws come in the reference's order (support videos, then query videos)
+        d = {"support_set": self.tf(sup_videos, train=train), "target_set": self.tf(tgt_videos, train=train),
+             "support_set_feature_teacher": torch.stack([self._feature(s[0], s[1]) for s in sup]).to(self.device),
+             "target_set_feature_teacher": torch.stack([self._feature(t[0], t[1]) for t in tgt]).to(self.device)}
+        d.update(self._labels(sup, tgt, self.c.way))
+        return {k: v.unsqueeze(0) for k, v in d.items()}
 
     def episode(self):
-        c = self.c
-        nq = c.query_per_class if self.train else c.query_per_class_test
-        batch_classes = random.sample(list(self.classes), c.way)
-        sup, tgt = [], []
-        for bl, bc in enumerate(batch_classes):
-            vids = self.classes[bc]
-            if len(vids) < c.shot + nq:
-                raise ValueError("class %s has %d videos, an episode needs %d" % (bc, len(vids), c.shot + nq))
-            idxs = random.sample(range(len(vids)), c.shot + nq)
-            for j, i in enumerate(idxs):
-                clip = torch.from_numpy(self._frames(np.load(os.path.join(self.root, bc, vids[i] + ".npy"), mmap_mode="r")).copy())
-                (sup if j < c.shot else tgt).append((clip, self._feature(bc, vids[i]), bl))
-        random.shuffle(sup)
-        random.shuffle(tgt)
-        # one transform call per set: the per-video flip / crop draws come in the reference's order (support videos, then query videos)
-        d = {"support_set": self.tf([s[0] for s in sup], train=self.train), "target_set": self.tf([t[0] for t in tgt], train=self.train),
-             "support_set_feature_teacher": torch.stack([s[1] for s in sup]).to(self.device), "target_set_feature_teacher": torch.stack([t[1] for t in tgt]).to(self.device),
-             "support_labels": torch.FloatTensor([s[2] for s in sup]), "target_labels": torch.FloatTensor([t[2] for t in tgt]),
-             "real_target_labels": torch.FloatTensor([t[2] for t in tgt]), "batch_class_list": torch.arange(c.way).float()}
-        return {k: v.unsqueeze(0) for k, v in d.items()}
+        train = self.train
+        sup, tgt = self._draw(train)
+        clip = lambda v: torch.from_numpy(np.ascontiguousarray(v[2][v[3]]))      # noqa: E731
+        return self._task([clip(s) for s in sup], [clip(t) for t in tgt], sup, tgt, train)
 
     def __iter__(self):
         for _ in range(self.length):
             yield self.episode()
+
+
+def jpeg_frame_index(rgb_path):
+    """read_dir (video_reader.py:118-196) without the split: -> ({class: {video: [frame file names]}}, {(class, video): [paths]}) of a
+    directory <rgb_path>/<class>/<video>/<frame>.jpg or an uncompressed .zip of the same tree (a member's last three path components;
+    the paths are then member names).  Classes, videos and frames sorted; the index of a directory equals that of its .zip."""
+    idx = {}
+    if rgb_path.endswith(".zip"):
+        with zipfile.ZipFile(rgb_path) as zf:
+            for name in zf.namelist():
+                parts = name.split("/")
+                if len(parts) >= 3 and parts[-1].endswith(".jpg"):
+                    idx.setdefault(parts[-3], {}).setdefault(parts[-2], []).append((parts[-1], name))
+    else:
+        for cname in os.listdir(rgb_path):
+            d = os.path.join(rgb_path, cname)
+            if not os.path.isdir(d):
+                continue
+            for vid in os.listdir(d):
+                vd = os.path.join(d, vid)
+                if os.path.isdir(vd):
+                    idx.setdefault(cname, {})[vid] = [(f, os.path.join(vd, f)) for f in os.listdir(vd) if f.endswith(".jpg")]
+    index, paths = {}, {}
+    for cname in sorted(idx):
+        index[cname] = {}
+        for vid in sorted(idx[cname]):
+            frames = sorted(idx[cname][vid])
+            index[cname][vid] = [f for f, _ in frames]
+            paths[(cname, vid)] = [p for _, p in frames]
+    return index, paths
+
+
+def read_split_lists(traintestlist, split):
+    """_select_fold (video_reader.py:305-319): {train,test}list{split:02d}.txt -> {"train": set, "test": set} of video names, normalised
+    as the reference does (spaces to '_', lower case, first token, basename without extension); a video folder v is matched as v.lower()"""
+    lists = {}
+    for name in ("train", "test"):
+        with open(os.path.join(traintestlist, "{}list{:02d}.txt".format(name, split))) as f:
+            data = [x.replace(" ", "_").lower() for x in f.readlines()]
+        data = [x.strip().split(" ")[0] for x in data]
+        lists[name] = {os.path.splitext(os.path.split(x)[1])[0] for x in data}
+    return lists
+
+
+class JpegFrameEpisodes(ClipDirectoryEpisodes):
+    """Episodes from the reference's own data layout (video_reader.VideoDataset, video_reader.py:118-485): JPEG frames
+    <rgb_path>/<class>/<video>/<frame>.jpg or an uncompressed .zip of that tree, split into train / test videos by the split lists
+    ({train,test}list{split:02d}.txt under `traintestlist`; without them every video serves both modes), teacher features from
+    <teacher_path>/<class>/<video>/ (the first file in sorted order, a float [seq_len, 2048] .npy).
+
+    Features are matched to videos BY NAME and a missing one raises.  The reference matches them by position in two separately built
+    lists (:197-260, :388-396), which silently pairs a video with another video's feature when a folder is missing on one side.
+
+    The draws are ClipDirectoryEpisodes' own (_draw: classes, videos, frames, shuffles, then flip / crop), so a seeded run picks the same
+    episode from a JPEG tree as from the .npy tree of the same decoded frames; only the seq_len selected files of a video are read.  The
+    frames are decoded on the GPU (ops.JpegPlan, csrc/jpeg.hip; bit-identical to PIL): episode() decodes and transforms on the current
+    stream; host_episode() hands trainloop.StreamedEpisodes the compressed bytes of the episode, packed into one pinned buffer with
+    their decode plan, in place of "frames"."""
+
+    def __init__(self, config, rgb_path, traintestlist=None, teacher_path=None, split=None, device="cuda", length=10 ** 9, train=True):
+        from . import ops
+        from .video_transform import GpuFrameTransform
+        self.c, self.root, self.froot, self.device, self.length, self.train = config, rgb_path, teacher_path, device, length, train
+        self.dataset = self
+        self.index, self._paths = jpeg_frame_index(rgb_path)
+        self.class_folders = list(self.index)          # the class id of the reference = the position in this list
+        self._zip = zipfile.ZipFile(rgb_path) if rgb_path.endswith(".zip") else None
+        lists = read_split_lists(traintestlist, getattr(config, "split", 3) if split is None else split) if traintestlist else None
+        self.splits = {True: {}, False: {}}
+        for cname, vids in self.index.items():
+            for vid, frames in vids.items():
+                if len(frames) < config.seq_len:
+                    continue
+                if lists is None:
+                    modes = (True, False)
+                else:
+                    v = vid.lower()
+                    modes = (True,) if v in lists["train"] else (False,) if v in lists["test"] else ()
+                for m in modes:
+                    self.splits[m].setdefault(cname, []).append(vid)
+        self._feat = {}
+        if teacher_path is not None:
+            for m in (True, False):
+                for cname, vids in self.splits[m].items():
+                    for vid in vids:
+                        d = os.path.join(teacher_path, cname, vid)
+                        files = sorted(os.listdir(d)) if os.path.isdir(d) else []
+                        if not files:
+                            raise ValueError("no teacher feature for video %s/%s under %s" % (cname, vid, teacher_path))
+                        self._feat[(cname, vid)] = os.path.join(d, files[0])
+        if len(self.splits[bool(train)]) < config.way:
+            raise ValueError("%s holds %d classes in the %s split, the episodes need %d"
+                             % (rgb_path, len(self.splits[bool(train)]), "train" if train else "test", config.way))
+        self.tf = GpuFrameTransform(config.img_size, device)
+        self._ring = ops.PinnedRing(6)
+
+    @property
+    def classes(self):
+        return self.splits[bool(self.train)]
+
+    def _classes(self, train):
+        return self.splits[bool(train)]
+
+    def _open(self, cname, vid):
+        p = self._paths[(cname, vid)]
+        return p, len(p)
+
+    def _read(self, path):
+        if self._zip is not None:
+            return self._zip.read(path)
+        with open(path, "rb") as f:
+            return f.read()
+
+    def _feature(self, cname, vid):
+        if self.froot is None:              # (the evaluator of a student needs no teacher features)
+            return torch.zeros(self.c.seq_len, 2048)
+        return torch.from_numpy(np.load(self._feat[(cname, vid)])).float()
+
+    def _plan(self, train):
+        from . import ops
+        sup, tgt = self._draw(train)
+        names = [v[2][i] for v in sup + tgt for i in v[3]]
+        plan = ops.JpegPlan([self._read(p) for p in names], names=names, ring=self._ring if torch.cuda.is_available() else None)
+        plan.check()                        # a malformed header names its file here
+        return sup, tgt, plan
+
+    def host_episode(self):
+        train = self.train                  # read once: an episode is wholly of one mode
+        sup, tgt, plan = self._plan(train)
+        shapes = plan.shapes()
+        if len(set(shapes)) != 1:
+            raise ValueError("StreamedEpisodes needs one frame resolution per episode (got %s): use the loader without --stream_inputs"
+                             % sorted(set(shapes)))
+        L = self.c.seq_len
+        params = [self.tf.draw(shapes[i * L][0], shapes[i * L][1], train) for i in range(len(sup) + len(tgt))]
+        d = {"jpeg": plan, "params": params, "features": torch.stack([self._feature(v[0], v[1]) for v in sup + tgt]), "ns": len(sup)}
+        d.update(self._labels(sup, tgt, self.c.way))
+        return d
+
+    def episode(self):
+        train = self.train
+        sup, tgt, plan = self._plan(train)
+        frames, _ = plan.decode(check=True)
+        L = self.c.seq_len
+        if torch.is_tensor(frames):
+            videos = [frames[i * L:(i + 1) * L] for i in range(len(sup) + len(tgt))]
+        else:
+            videos = [torch.stack(frames[i * L:(i + 1) * L]) for i in range(len(sup) + len(tgt))]
+        return self._task(videos[:len(sup)], videos[len(sup):], sup, tgt, train)
 
 
 def schedule_from_args(args):
@@ -229,7 +403,12 @@ def schedule_from_args(args):
 
 
 def main(argv=None):
-    args = args_check(build_parser().parse_args(argv))
+    parser = build_parser()
+    args = args_check(parser.parse_args(argv))
+    if args.rgb_path and args.data_dir:
+        parser.error("--rgb_path and --data_dir are exclusive")
+    if args.rgb_path and not args.teacher_path:
+        parser.error("--rgb_path needs --teacher_path (the distillation loss reads the teacher features)")
     from .parallel import init_distributed
     rank, world, dev = init_distributed()
     args.device = dev
@@ -238,8 +417,9 @@ def main(argv=None):
     torch.manual_seed(args.seed)                  # identical initial weights on every rank (make() also broadcasts them)
     sched = schedule_from_args(args)
     loader = None
-    if args.data_dir:
-        loader = ClipDirectoryEpisodes(args, args.data_dir, args.feature_dir, device=dev)
+    if args.data_dir or args.rgb_path:
+        loader = (JpegFrameEpisodes(args, args.rgb_path, args.traintestlist, args.teacher_path, split=args.split, device=dev) if args.rgb_path
+                  else ClipDirectoryEpisodes(args, args.data_dir, args.feature_dir, device=dev))
         if args.stream_inputs and torch.device(dev).type == "cuda":
             # the loader beside the compute (trainwandb.py:87-88: a DataLoader worker): a prefetch thread reads and pins the next episodes,
             # a copy stream uploads the uint8 frames and runs the frame transform into one of three static input sets

@@ -318,7 +318,14 @@ class StreamedEpisodes:
     compute stream waits for the set's `ready` event; the copy stream, before it overwrites a set, for the events the loop recorded on
     every stream that read it (release(): the lane's streams and the weight-gradient stream after the episode's backward pass was
     queued - nothing on the compute side ever waits for the loader).  With cross-episode pipelining three episodes are in flight
-    (backward i, forward i + 1, staging i + 2) and the loader stages one episode ahead of the loop's request: hence sets >= 4."""
+    (backward i, forward i + 1, staging i + 2) and the loader stages one episode ahead of the loop's request: hence sets >= 4.
+
+    A source may hand over COMPRESSED frames instead (train.JpegFrameEpisodes): "jpeg" = an ops.JpegPlan (the JPEG bytes, descriptors and
+    table pool in one pinned buffer) in place of "frames"; the copy stream then uploads it and runs the three decode launches into the
+    set's uint8 buffer before the frame transform.  The decoder's status words are read when a later episode is staged, without a
+    synchronisation: a malformed frame raises ValueError (naming its file) an episode or two late.  One prefetch generation per mode:
+    when dataset.train changes (test() in mid-training) the producer is stopped, queued and held episodes are dropped and a producer
+    for the new mode starts."""
 
     def __init__(self, source, config, device, sets=4, prefetch=2):
         import queue
@@ -337,20 +344,43 @@ class StreamedEpisodes:
         self._stop = threading.Event()
         self._thread = None
         self._threading = threading
+        self._queue_mod = queue
+        self._prefetch = max(1, int(prefetch))
+        self._gen = 0                       # prefetch generation: one per mode (train / test) the loader serves in turn
+        self._mode = None
+        self._jpeg_pending = []             # (set index, event, pinned status words, plan) of staged JPEG episodes, not yet checked
         self.length = getattr(source, "length", 10 ** 9)
         self.staged = 0
 
     # ---- host side (prefetch thread)
-    def _produce(self):
+    def _produce(self, q, stop):
         try:
             n = 0
-            while not self._stop.is_set() and n < self.length:
+            while not stop.is_set() and n < self.length:
                 h = dict(self.source.host_episode())
+                if "jpeg" in h:             # compressed frames: the source packed them (and their decode plan) into pinned memory
+                    slot = self._pins[n % len(self._pins)]
+                    if slot is None or slot.get("frames") is not None or slot["features"].shape != h["features"].shape:
+                        slot = self._pins[n % len(self._pins)] = {"frames": None, "event": None,
+                                                                  "features": torch.empty(h["features"].shape, dtype=torch.float32).pin_memory()}
+                    if slot["event"] is not None:
+                        slot["event"].synchronize()
+                        slot["event"] = None
+                    slot["features"].copy_(h["features"])
+                    h["features"], h["_slot"] = slot["features"], slot
+                    n += 1
+                    while not stop.is_set():
+                        try:
+                            q.put(h, timeout=0.1)
+                            break
+                        except Exception:      # queue.Full
+                            continue
+                    continue
                 if h["frames"].is_pinned() and h["features"].is_pinned() and h["features"].dtype is torch.float32:
                     n += 1      # the source decodes into pinned memory of its own (and keeps it alive until the episode has been staged)
-                    while not self._stop.is_set():
+                    while not stop.is_set():
                         try:
-                            self._q.put(h, timeout=0.1)
+                            q.put(h, timeout=0.1)
                             break
                         except Exception:
                             continue
@@ -367,23 +397,27 @@ class StreamedEpisodes:
                 slot["features"].copy_(h["features"])
                 h["frames"], h["features"], h["_slot"] = slot["frames"], slot["features"], slot
                 n += 1
-                while not self._stop.is_set():
+                while not stop.is_set():
                     try:
-                        self._q.put(h, timeout=0.1)
+                        q.put(h, timeout=0.1)
                         break
                     except Exception:      # queue.Full
                         continue
         except BaseException as e:      # surfaces in the training thread
-            self._q.put(e)
+            q.put(e)
         finally:
-            self._q.put(None)
+            q.put(None)
 
     def _set(self, k, h):
         s = self.sets[k]
-        F_, H, W, _ = h["frames"].shape
+        if "jpeg" in h:
+            shapes = h["jpeg"].shapes()
+            F_, H, W = len(shapes), shapes[0][0], shapes[0][1]
+        else:
+            F_, H, W, _ = h["frames"].shape
         N, L, D = h["features"].shape
         S = self.c.img_size
-        if s is None or s["u8"].shape != h["frames"].shape or s["feat"].shape != h["features"].shape:
+        if s is None or tuple(s["u8"].shape) != (F_, H, W, 3) or s["feat"].shape != h["features"].shape:
             s = self.sets[k] = {"u8": torch.empty((F_, H, W, 3), dtype=torch.uint8, device=self.device),
                                 "x": torch.empty((F_, S, S, 4), dtype=torch.float32, device=self.device),
                                 "feat": torch.empty((N, L, D), dtype=torch.float32, device=self.device),
@@ -397,11 +431,23 @@ class StreamedEpisodes:
         self.staged += 1
         s = self._set(k, h)
         L = h["features"].shape[1]
+        self._jpeg_check(k)
         with torch.cuda.stream(self.copy):
             for ev in s["free"]:
                 self.copy.wait_event(ev)                   # every stream that read this set last time has passed
             s["free"] = []
-            s["u8"].copy_(h["frames"], non_blocking=True)
+            if "jpeg" in h:
+                # upload of the packed bytes + descriptors + table pool, the three decode launches (csrc/jpeg.hip) into the set's uint8
+                # frames; the status words go to pinned memory and are read when a later episode is staged (no synchronisation here)
+                plan = h["jpeg"]
+                _, status = plan.decode(out=s["u8"], check=False, device=self.device)
+                words = torch.empty(status.shape, dtype=torch.int32).pin_memory()
+                words.copy_(status, non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record(self.copy)
+                self._jpeg_pending.append((k, ev, words, plan))
+            else:
+                s["u8"].copy_(h["frames"], non_blocking=True)
             s["feat"].copy_(h["features"], non_blocking=True)
             if h.get("_slot") is not None:                 # the pinned slot is free again once these copies have run
                 ev = torch.cuda.Event()
@@ -439,15 +485,59 @@ class StreamedEpisodes:
             ev.record(st)
             s["free"].append(ev)
 
+    def _jpeg_check(self, k=None):
+        """read the status words of staged JPEG episodes whose copy has finished (and, for set k, which is about to be overwritten, wait for
+        it: it was staged several episodes ago) -> ValueError naming the frame file the GPU decoder stopped on"""
+        keep = []
+        for item in self._jpeg_pending:
+            kk, ev, words, plan = item
+            if kk == k or k is None:
+                ev.synchronize()
+            elif not ev.query():
+                keep.append(item)
+                continue
+            plan.raise_on_status(words)
+        self._jpeg_pending = keep
+
+    def _stop_thread(self):
+        if self._thread is not None:
+            self._stop.set()
+            while self._thread.is_alive():              # drain: a producer blocked in put() sees the stop flag
+                try:
+                    self._q.get(timeout=0.05)
+                except self._queue_mod.Empty:
+                    pass
+            self._thread.join()
+            self._thread = None
+
+    def _start(self, mode):
+        """a new prefetch generation for `mode` (dataset.train): the previous producer is stopped and its queued episodes dropped"""
+        self._stop_thread()
+        self._gen += 1
+        self._mode = mode
+        self._stop = self._threading.Event()
+        self._q = self._queue_mod.Queue(maxsize=self._prefetch)
+        self._thread = self._threading.Thread(target=self._produce, args=(self._q, self._stop), daemon=True)
+        self._thread.start()
+        return self._gen
+
+    def _dataset_mode(self):
+        return bool(getattr(self.dataset, "train", True))
+
     def __iter__(self):
-        if self._thread is None:
-            self._thread = self._threading.Thread(target=self._produce, daemon=True)
-            self._thread.start()
+        # one prefetch generation per mode: test() in mid-training switches dataset.train and iterates again, the training loop resumes
+        # afterwards - each switch stops the producer, drops the queued and held episodes and starts a producer for the new mode, so a
+        # test never scores training-mode episodes and training never consumes test-split ones (ADVICE.md, first finding)
+        mode = self._dataset_mode()
+        gen = self._start(mode) if self._thread is None or self._mode != mode else self._gen
         # staging runs ONE episode ahead of the loop: the copy + transform of episode i + 1 are queued (on the copy stream) before the loop
         # queues episode i's forward pass, so they execute under it instead of in front of episode i + 1 (round 5: 0.90 -> see
         # profiles/r05_bench.json `stream_inputs` of the resident rate); one more input set is in flight for it (sets >= 4)
         held = None
         while True:
+            if gen != self._gen or self._dataset_mode() != self._mode:
+                held = None
+                gen = self._start(self._dataset_mode())
             h = self._q.get()
             if isinstance(h, BaseException):
                 raise h
@@ -460,7 +550,8 @@ class StreamedEpisodes:
             held = td
 
     def close(self):
-        self._stop.set()
+        self._stop_thread()
+        self._jpeg_check()
 
 
 def release_inputs(task_dict):
