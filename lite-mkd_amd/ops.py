@@ -559,18 +559,29 @@ def _desc_arg(d):
 # (csrc/common.h amax_commit_stat) and h2_fence_step() - once per episode, no host synchronisation: the verdict is read an episode or two
 # later - lets lmkd_h2_fence_eval judge the counts.  A flagged site stays flagged (h2_fence_reset() clears): its tensor's maximum is
 # withheld from the convolutions, which then run the three-plane form, and lmkd_conv_h2_fallbacks() counts those launches.
+# Per lane (LANE): a pending entry carries the lane it was written on and only that lane's h2_fence_step() judges it - on the lane's
+# stream, which is ordered behind that episode's producers and no other's - and a site keeps reference words per lane, so no evaluation
+# writes words that another lane's producers read.  The sequential loop runs on lane 0 alone; in the pipelined loop each lane compares
+# against its own previous episode.
 H2_FENCE = os.environ.get("LMKD_H2_FENCE", "1") != "0"      # (bench.py A/B: LMKD_H2_FENCE=0 runs the two-plane arithmetic unfenced)
-_FENCE_SITES = {}        # site -> {"ref": persistent words, "bad": bool}
-_FENCE_PENDING = []      # (site, words) written since the last h2_fence_step()
+_FENCE_SITES = {}        # site -> {"ref": {lane: persistent words}, "bad": bool}
+_FENCE_PENDING = []      # (site, lane, words) written since that lane's last h2_fence_step()
 _FENCE_INFLIGHT = []     # (event, pinned host flags, [sites], keep-alive)
 
 
-def _fence_site(site, dev):
-    e = _FENCE_SITES.get(site)
-    if e is None:
-        e = _FENCE_SITES[site] = {"ref": torch.zeros(lib().value("lmkd_amax_words"), dtype=torch.int32, device=dev), "bad": False}
-        _audit.audit_ok(e["ref"], "persistent: a site's reference words are never freed")
-    return e
+def _fence_watch(site, words, dev):
+    """a launch is about to write the words of a tensor of `site` (None: not fenced): in training, outside a capture, they wait for this
+    lane's next h2_fence_step() -> address of the lane's reference words of the site, for the launch to count against (else None)"""
+    if site is None or not (H2_FENCE and torch.is_grad_enabled()) or torch.cuda.is_current_stream_capturing():
+        return None
+    if len(_FENCE_PENDING) > 4096:      # nobody calls h2_fence_step(): keep the newest
+        del _FENCE_PENDING[:2048]
+    refs = _FENCE_SITES.setdefault(site, {"ref": {}, "bad": False})["ref"]
+    if LANE[0] not in refs:
+        refs[LANE[0]] = torch.zeros(lib().value("lmkd_amax_words"), dtype=torch.int32, device=dev)
+        _audit.audit_ok(refs[LANE[0]], "persistent: a site's reference words are never freed")
+    _FENCE_PENDING.append((site, LANE[0], words))
+    return refs[LANE[0]].data_ptr()
 
 
 def h2_fence_reset():
@@ -600,29 +611,30 @@ def _fence_poll(wait=False):
 
 
 def h2_fence_step(wait=False):
-    """judge the tensors written since the last call (one small launch + one 4-bytes-per-tensor copy to pinned memory, both asynchronous)
-    and take in the verdicts that have arrived.  Call once per episode, on a stream that is ordered behind the episode's producers (after
-    backward()).  wait=True (tests): also wait for this call's verdicts."""
+    """judge the tensors this lane (LANE) has written since its last call (one small launch + one 4-bytes-per-tensor copy to pinned memory,
+    both asynchronous) and take in the verdicts that have arrived.  Call once per episode, under the episode's lane, on a stream that is
+    ordered behind the episode's producers (after backward()).  wait=True (tests, bench.py): also wait for every verdict in flight."""
     if not _FENCE_PENDING and not _FENCE_INFLIGHT:
         return
     if torch.cuda.is_current_stream_capturing():
         return
     _fence_poll()
-    if _FENCE_PENDING:
-        pend = list(_FENCE_PENDING)
-        del _FENCE_PENDING[:]
+    lane = LANE[0]
+    pend = [e for e in _FENCE_PENDING if e[1] == lane]
+    if pend:
+        _FENCE_PENDING[:] = [e for e in _FENCE_PENDING if e[1] != lane]
         n = len(pend)
-        dev = pend[0][1].device
+        dev = pend[0][2].device
         P = ctypes.c_void_p * n
-        words = P(*[w.data_ptr() for _, w in pend])
-        refs = P(*[_FENCE_SITES[site]["ref"].data_ptr() for site, _ in pend])
+        words = P(*[w.data_ptr() for _, _, w in pend])
+        refs = P(*[_FENCE_SITES[site]["ref"][lane].data_ptr() for site, _, _ in pend])
         flags = torch.empty(n, dtype=torch.int32, device=dev)
         lib().call("lmkd_h2_fence_eval", words, refs, n, _p(flags), _stream())
         host = torch.empty(n, dtype=torch.int32).pin_memory()
         host.copy_(flags, non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
-        _FENCE_INFLIGHT.append((ev, host, [site for site, _ in pend], (pend, flags)))
+        _FENCE_INFLIGHT.append((ev, host, [site for site, _, _ in pend], (pend, flags)))
     if wait:
         _fence_poll(wait=True)
 
@@ -634,17 +646,9 @@ def _amax_out(t, site=None):
         return None
     w = _amax_slot(t.device)
     t._lmkd_amax = w
-    d = AmaxDesc(None, None, _pw(w), None, 0)
-    if site is not None and H2_FENCE and torch.is_grad_enabled() and not torch.cuda.is_current_stream_capturing():      # (training: the loops call h2_fence_step once per episode)
-        if len(_FENCE_PENDING) > 4096:      # nobody calls h2_fence_step(): keep the newest
-            del _FENCE_PENDING[:2048]
-        e = _fence_site(site, t.device)
-        d.ref_words = e["ref"].data_ptr()
+    if site is not None:
         t._lmkd_site = site
-        _FENCE_PENDING.append((site, w))
-    elif site is not None:
-        t._lmkd_site = site
-    return d
+    return AmaxDesc(None, None, _pw(w), _fence_watch(site, w, t.device), 0)
 
 
 _AMAX_ATTRS = ("_lmkd_amax", "_lmkd_site", "_lmkd_pre_amax", "_lmkd_pre_site")
@@ -1046,10 +1050,7 @@ def bn_stats_train(part, count, gamma, beta, running_mean, running_var, seg=None
     T, C, _ = part.shape
     d = None
     if bound is not None:
-        d = AmaxDesc(_pw(bound[0]), None, _pw(bound[1]), None, 0)
-        if bound[2] is not None and H2_FENCE and torch.is_grad_enabled() and not torch.cuda.is_current_stream_capturing():
-            d.ref_words = _fence_site(bound[2], part.device)["ref"].data_ptr()
-            _FENCE_PENDING.append((bound[2], bound[1]))
+        d = AmaxDesc(_pw(bound[0]), None, _pw(bound[1]), _fence_watch(bound[2], bound[1], part.device), 0)
     if seg is not None:
         T0, count0 = seg
         if running_mean is not None or running_var is not None:

@@ -94,7 +94,7 @@ def build_parser():
                    "f32x3 = every fp32 product from an exact 3-way bf16 split, six products (the library's default arithmetic); "
                    "f32native = v_mfma_f32_32x32x2_f32, bf16 = bf16 tensors + bf16 MFMA (the reference's autocast path, trainwandb.py:20,126)")
     p.add_argument("--no_stream_inputs", dest="stream_inputs", action="store_false", help="with --data_dir: read, upload and transform every episode on "
-                   "the training thread (default: a prefetch thread + copy stream + three static input sets, trainloop.StreamedEpisodes; needs one "
+                   "the training thread (default: a prefetch thread + copy stream + four static input sets, trainloop.StreamedEpisodes; needs one "
                    "frame resolution per episode)")
     p.add_argument("--serial", action="store_true", help="single-stream schedule (Schedule.serial())")
     p.add_argument("--two_call", action="store_true", help="round 3's schedule (two trunk calls on two streams, no cross-episode pipelining) instead of "
@@ -216,7 +216,7 @@ class ClipDirectoryEpisodes:
         sup, tgt = self._draw(train)
         vids = [torch.from_numpy(np.ascontiguousarray(v[2][v[3]])) for v in sup + tgt]
         if len({tuple(v.shape[1:3]) for v in vids}) != 1:
-            raise ValueError("StreamedEpisodes needs one frame resolution per episode (got %s): use the loader without --stream_inputs"
+            raise ValueError("StreamedEpisodes needs one frame resolution per episode (got %s): run with --no_stream_inputs"
                              % sorted({tuple(v.shape[1:3]) for v in vids}))
         params = [self.tf.draw(v.shape[1], v.shape[2], train) for v in vids]
         d = {"frames": torch.cat(vids, 0), "params": params, "features": torch.stack([self._feature(v[0], v[1]) for v in sup + tgt]),
@@ -372,7 +372,7 @@ class JpegFrameEpisodes(ClipDirectoryEpisodes):
         sup, tgt, plan = self._plan(train)
         shapes = plan.shapes()
         if len(set(shapes)) != 1:
-            raise ValueError("StreamedEpisodes needs one frame resolution per episode (got %s): use the loader without --stream_inputs"
+            raise ValueError("StreamedEpisodes needs one frame resolution per episode (got %s): run with --no_stream_inputs"
                              % sorted(set(shapes)))
         L = self.c.seq_len
         params = [self.tf.draw(shapes[i * L][0], shapes[i * L][1], train) for i in range(len(sup) + len(tgt))]
@@ -422,7 +422,7 @@ def main(argv=None):
                   else ClipDirectoryEpisodes(args, args.data_dir, args.feature_dir, device=dev))
         if args.stream_inputs and torch.device(dev).type == "cuda":
             # the loader beside the compute (trainwandb.py:87-88: a DataLoader worker): a prefetch thread reads and pins the next episodes,
-            # a copy stream uploads the uint8 frames and runs the frame transform into one of three static input sets
+            # a copy stream uploads the uint8 frames and runs the frame transform into one of four static input sets
             loader = TL.StreamedEpisodes(loader, args, dev)
     student, teacher, loader, distiller, accuracy_fn, _, optimizer, scheduler = TL.make(args, video_loader=loader, base_seed=args.seed, schedule=sched)
     if args.teacher_checkpoint:

@@ -5,6 +5,8 @@
   * scheduler.step() runs every episode (:145) — milestones are in episodes;
   * only the CE term carries the 1/16 accumulation scaling (distillers.py:326-335).
 wandb / checkpoint-file side effects are replaced by an optional `log` callback."""
+import itertools
+
 import numpy as np
 import torch
 
@@ -172,15 +174,25 @@ def _labels_to_device(t, dev, dtype):
 def train_task(task_dict, student, teacher, distiller, accuracy_fn, config):
     """trainwandb.py:190-287 for the logits-based distillers."""
     out = _train_task_prepared(prepare_task(task_dict, config.device), student, teacher, distiller, accuracy_fn, config)
-    release_inputs(task_dict)
+    end_episode(task_dict)
     return out
 
 
 def _train_task_prepared(prepared, student, teacher, distiller, accuracy_fn, config):
     task_loss, task_accuracy = _episode_forward(prepared, student, teacher, distiller, accuracy_fn, config)
     task_loss.backward(retain_graph=False)
-    ops.h2_fence_step()      # fp32h2: the range fence judges this episode's tensors (asynchronous; a no-op in the other arithmetics)
     return task_loss.detach(), task_accuracy, {"accuracy": task_accuracy}
+
+
+def end_episode(task_dict, train=True):
+    """every consumer of a task_dict calls this once the work of its episode has been queued, under the episode's lane: in training the
+    range fence judges this lane's words (fp32h2, asynchronous; a no-op in the other arithmetics and inside a capture), then a
+    StreamedEpisodes loader gets the episode's input set back (behind every stream that read it)"""
+    if train:
+        ops.h2_fence_step()
+    tag = task_dict.get("_input_set") if isinstance(task_dict, dict) else None
+    if tag is not None:
+        tag[0].release(tag[1])
 
 
 def _episode_forward(prepared, student, teacher, distiller, accuracy_fn, config):
@@ -269,7 +281,7 @@ class PipelinedEpisodes:
                 if self.bwd_done is not None:
                     main.wait_event(self.bwd_done)       # gradients accumulate in episode order
                 loss.backward(retain_graph=False)
-                ops.h2_fence_step()      # fp32h2: the range fence judges this episode's tensors (asynchronous)
+                end_episode(task_dict)
                 # the lane's side / auxiliary streams wrote parameter gradients directly (autograd got None and joined nothing): the
                 # event that orders the NEXT backward's accumulations must cover them
                 d = torch.device(dev)
@@ -280,7 +292,6 @@ class PipelinedEpisodes:
                 ev = torch.cuda.Event()
                 ev.record(main)
                 self.bwd_done = ev
-                release_inputs(task_dict)      # a StreamedEpisodes loader may now re-stage the episode's input set (behind every stream that read it)
         finally:
             ops.set_lane(0)
         return loss.detach(), acc
@@ -317,8 +328,12 @@ class StreamedEpisodes:
     (Resize -> crop / flip -> ToTensor, video_transform.GpuFrameTransform.batch) there too, into one of `sets` static input sets.  The
     compute stream waits for the set's `ready` event; the copy stream, before it overwrites a set, for the events the loop recorded on
     every stream that read it (release(): the lane's streams and the weight-gradient stream after the episode's backward pass was
-    queued - nothing on the compute side ever waits for the loader).  With cross-episode pipelining three episodes are in flight
-    (backward i, forward i + 1, staging i + 2) and the loader stages one episode ahead of the loop's request: hence sets >= 4.
+    queued - nothing on the compute side ever waits for the loader).
+
+    A set belongs to one episode from _stage() until the consumer's end_episode() (release()); staging into a set that is still busy
+    raises.  When episode i + 1 is staged (one episode ahead of the loop's request), the sets still busy are those of the PIPELINE_DEPTH
+    episodes whose backward passes PipelinedEpisodes has not queued yet (i - PIPELINE_DEPTH ... i - 1), of episode i (staged, about to be
+    handed out) and of episode i + 1 itself: hence sets >= PIPELINE_DEPTH + 2, and the constructor raises `sets` to that.
 
     A source may hand over COMPRESSED frames instead (train.JpegFrameEpisodes): "jpeg" = an ops.JpegPlan (the JPEG bytes, descriptors and
     table pool in one pinned buffer) in place of "frames"; the copy stream then uploads it and runs the three decode launches into the
@@ -334,7 +349,7 @@ class StreamedEpisodes:
         self.source, self.c, self.device = source, config, torch.device(device)
         self.tf = GpuFrameTransform(config.img_size, self.device)
         self.copy = torch.cuda.Stream(device=self.device)
-        self.nsets = max(3, int(sets))
+        self.nsets = max(PIPELINE_DEPTH + 2, int(sets))
         self.sets = [None] * self.nsets
         self.dataset = getattr(source, "dataset", source)
         self._q = queue.Queue(maxsize=max(1, int(prefetch)))
@@ -348,6 +363,7 @@ class StreamedEpisodes:
         self._prefetch = max(1, int(prefetch))
         self._gen = 0                       # prefetch generation: one per mode (train / test) the loader serves in turn
         self._mode = None
+        self._ahead = None                  # the current generation's episode staged ahead of the loop's request, not handed out yet
         self._jpeg_pending = []             # (set index, event, pinned status words, plan) of staged JPEG episodes, not yet checked
         self.length = getattr(source, "length", 10 ** 9)
         self.staged = 0
@@ -357,56 +373,37 @@ class StreamedEpisodes:
         try:
             n = 0
             while not stop.is_set() and n < self.length:
-                h = dict(self.source.host_episode())
-                if "jpeg" in h:             # compressed frames: the source packed them (and their decode plan) into pinned memory
-                    slot = self._pins[n % len(self._pins)]
-                    if slot is None or slot.get("frames") is not None or slot["features"].shape != h["features"].shape:
-                        slot = self._pins[n % len(self._pins)] = {"frames": None, "event": None,
-                                                                  "features": torch.empty(h["features"].shape, dtype=torch.float32).pin_memory()}
-                    if slot["event"] is not None:
-                        slot["event"].synchronize()
-                        slot["event"] = None
-                    slot["features"].copy_(h["features"])
-                    h["features"], h["_slot"] = slot["features"], slot
-                    n += 1
-                    while not stop.is_set():
-                        try:
-                            q.put(h, timeout=0.1)
-                            break
-                        except Exception:      # queue.Full
-                            continue
-                    continue
-                if h["frames"].is_pinned() and h["features"].is_pinned() and h["features"].dtype is torch.float32:
-                    n += 1      # the source decodes into pinned memory of its own (and keeps it alive until the episode has been staged)
-                    while not stop.is_set():
-                        try:
-                            q.put(h, timeout=0.1)
-                            break
-                        except Exception:
-                            continue
-                    continue
-                slot = self._pins[n % len(self._pins)]
-                if slot is None or slot["frames"].shape != h["frames"].shape or slot["features"].shape != h["features"].shape:
-                    slot = self._pins[n % len(self._pins)] = {"frames": torch.empty(h["frames"].shape, dtype=torch.uint8).pin_memory(),
-                                                              "features": torch.empty(h["features"].shape, dtype=torch.float32).pin_memory(),
-                                                              "event": None}
-                if slot["event"] is not None:
-                    slot["event"].synchronize()            # (host wait in the prefetch thread: the copy that read this slot has finished)
-                    slot["event"] = None
-                slot["frames"].copy_(h["frames"])
-                slot["features"].copy_(h["features"])
-                h["frames"], h["features"], h["_slot"] = slot["frames"], slot["features"], slot
+                h = self._pinned(dict(self.source.host_episode()), n)
                 n += 1
                 while not stop.is_set():
                     try:
                         q.put(h, timeout=0.1)
                         break
-                    except Exception:      # queue.Full
+                    except self._queue_mod.Full:
                         continue
         except BaseException as e:      # surfaces in the training thread
             q.put(e)
         finally:
             q.put(None)
+
+    def _pinned(self, h, n):
+        """the episode's frames and features in pinned memory.  A source that decodes into pinned memory of its own keeps it alive until the
+        episode has been staged; anything else is copied into slot n of the ring.  (Compressed frames come packed in pinned memory.)"""
+        dtypes = {"features": torch.float32} if "jpeg" in h else {"frames": torch.uint8, "features": torch.float32}
+        if all(h[k].is_pinned() for k in dtypes) and h["features"].dtype is torch.float32:
+            return h
+        slot = self._pins[n % len(self._pins)]
+        if slot is None or {k: t.shape for k, t in slot["host"].items()} != {k: h[k].shape for k in dtypes}:
+            slot = self._pins[n % len(self._pins)] = {"host": {k: torch.empty(h[k].shape, dtype=dt).pin_memory() for k, dt in dtypes.items()},
+                                                      "event": None}
+        if slot["event"] is not None:
+            slot["event"].synchronize()            # (host wait in the prefetch thread: the copy that read this slot has finished)
+            slot["event"] = None
+        for k, t in slot["host"].items():
+            t.copy_(h[k])
+            h[k] = t
+        h["_slot"] = slot
+        return h
 
     def _set(self, k, h):
         s = self.sets[k]
@@ -418,18 +415,23 @@ class StreamedEpisodes:
         N, L, D = h["features"].shape
         S = self.c.img_size
         if s is None or tuple(s["u8"].shape) != (F_, H, W, 3) or s["feat"].shape != h["features"].shape:
-            s = self.sets[k] = {"u8": torch.empty((F_, H, W, 3), dtype=torch.uint8, device=self.device),
-                                "x": torch.empty((F_, S, S, 4), dtype=torch.float32, device=self.device),
-                                "feat": torch.empty((N, L, D), dtype=torch.float32, device=self.device),
-                                "ready": torch.cuda.Event(), "free": []}
-            for t in (s["u8"], s["x"], s["feat"]):
-                ops._audit.audit_ok(t, "static input set: released to the copy stream through the events of release()")
+            # allocated on the copy stream, which writes them; the streams that read a set recorded themselves on its tensors in release(),
+            # so the allocator keeps the blocks of a replaced set until those readers have passed
+            with torch.cuda.stream(self.copy):
+                s = self.sets[k] = {"u8": torch.empty((F_, H, W, 3), dtype=torch.uint8, device=self.device),
+                                    "x": torch.empty((F_, S, S, 4), dtype=torch.float32, device=self.device),
+                                    "feat": torch.empty((N, L, D), dtype=torch.float32, device=self.device),
+                                    "ready": torch.cuda.Event(), "free": [], "busy": False}
         return s
 
     def _stage(self, h):
         k = self.staged % self.nsets
+        if self.sets[k] is not None and self.sets[k]["busy"]:
+            raise RuntimeError("StreamedEpisodes: input set %d of %d is still busy: its episode was not released (trainloop.end_episode); "
+                               "PIPELINE_DEPTH = %d needs %d sets" % (k, self.nsets, PIPELINE_DEPTH, PIPELINE_DEPTH + 2))
         self.staged += 1
         s = self._set(k, h)
+        s["busy"] = True
         L = h["features"].shape[1]
         self._jpeg_check(k)
         with torch.cuda.stream(self.copy):
@@ -466,13 +468,11 @@ class StreamedEpisodes:
         return td
 
     def release(self, k):
-        """the episode that read set k has been queued completely (forward and backward): record where every stream that may still read
-        the set stands - the copy stream waits for these before it overwrites the set"""
+        """the episode that read set k has been queued completely (end_episode): record where every stream that may still read the set
+        stands - the copy stream waits for these before it overwrites the set - and record those streams on the set's tensors"""
         s = self.sets[k]
-        if s is None:
-            return
-        # the streams of the lane the episode ran on (release() is called under that lane: PipelinedEpisodes._backward, train_task) and the
-        # weight-gradient stream - not every stream of every lane (twice as many events to record and for the copy stream to wait for)
+        # the streams of the lane the episode ran on (end_episode runs under that lane) and the weight-gradient stream - not every stream of
+        # every lane (twice as many events to record and for the copy stream to wait for)
         streams = [torch.cuda.current_stream(self.device)] + list(ops._WG_STREAM.values())
         for table in (ops._side_streams, ops._aux_streams, ops._lane_mains):
             streams += [st for key, st in table.items() if key[2] == ops.LANE[0]]
@@ -484,6 +484,9 @@ class StreamedEpisodes:
             ev = torch.cuda.Event()
             ev.record(st)
             s["free"].append(ev)
+            for t in (s["u8"], s["x"], s["feat"]):
+                t.record_stream(st)
+        s["busy"] = False
 
     def _jpeg_check(self, k=None):
         """read the status words of staged JPEG episodes whose copy has finished (and, for set k, which is about to be overwritten, wait for
@@ -511,8 +514,10 @@ class StreamedEpisodes:
             self._thread = None
 
     def _start(self, mode):
-        """a new prefetch generation for `mode` (dataset.train): the previous producer is stopped and its queued episodes dropped"""
+        """a new prefetch generation for `mode` (dataset.train): the previous producer is stopped, its queued episodes and the one it
+        staged ahead are dropped"""
         self._stop_thread()
+        self._unstage()
         self._gen += 1
         self._mode = mode
         self._stop = self._threading.Event()
@@ -524,6 +529,12 @@ class StreamedEpisodes:
     def _dataset_mode(self):
         return bool(getattr(self.dataset, "train", True))
 
+    def _unstage(self):
+        """drop the episode staged ahead: it was never handed out, only the copy stream has touched its set"""
+        if self._ahead is not None:
+            self.sets[self._ahead["_input_set"][1]]["busy"] = False
+            self._ahead = None
+
     def __iter__(self):
         # one prefetch generation per mode: test() in mid-training switches dataset.train and iterates again, the training loop resumes
         # afterwards - each switch stops the producer, drops the queued and held episodes and starts a producer for the new mode, so a
@@ -532,33 +543,27 @@ class StreamedEpisodes:
         gen = self._start(mode) if self._thread is None or self._mode != mode else self._gen
         # staging runs ONE episode ahead of the loop: the copy + transform of episode i + 1 are queued (on the copy stream) before the loop
         # queues episode i's forward pass, so they execute under it instead of in front of episode i + 1 (round 5: 0.90 -> see
-        # profiles/r05_bench.json `stream_inputs` of the resident rate); one more input set is in flight for it (sets >= 4)
-        held = None
-        while True:
-            if gen != self._gen or self._dataset_mode() != self._mode:
-                held = None
-                gen = self._start(self._dataset_mode())
-            h = self._q.get()
-            if isinstance(h, BaseException):
-                raise h
-            td = self._stage(h) if h is not None else None
-            if held is not None:
-                torch.cuda.current_stream(self.device).wait_event(self.sets[held["_input_set"][1]]["ready"])
-                yield held
-            if td is None:
-                return
-            held = td
+        # profiles/r05_bench.json `stream_inputs` of the resident rate); one more input set is in flight for it
+        try:
+            while True:
+                if gen != self._gen or self._dataset_mode() != self._mode:
+                    gen = self._start(self._dataset_mode())
+                h = self._q.get()
+                if isinstance(h, BaseException):
+                    raise h
+                td, self._ahead = self._ahead, (self._stage(h) if h is not None else None)
+                if td is not None:
+                    torch.cuda.current_stream(self.device).wait_event(self.sets[td["_input_set"][1]]["ready"])
+                    yield td
+                if h is None:
+                    return
+        finally:                            # the consumer has stopped (or an error): unless a later generation took over, drop what is staged
+            if gen == self._gen:
+                self._unstage()
 
     def close(self):
         self._stop_thread()
         self._jpeg_check()
-
-
-def release_inputs(task_dict):
-    """tell a StreamedEpisodes loader that the episode of this task_dict has been queued completely (a no-op for any other loader)"""
-    tag = task_dict.get("_input_set") if isinstance(task_dict, dict) else None
-    if tag is not None:
-        tag[0].release(tag[1])
 
 
 def init_model(config):
@@ -682,13 +687,14 @@ class GraphedEpisode:
         return (all(task_dict[k] is ent["task"][k] for k in self.KEYS)
                 and tuple(task_dict[k]._version for k in self.KEYS) == ent["versions"])
 
-    def _replay(self, ent):
+    def _replay(self, ent, task_dict):
         ops.wait_weight_grads()                                        # an eager episode's weight gradients may still be in flight
         ops.refresh_packs()
         ent["slots"].stage(self._seeds(ent["slots"].used))
         ent["graph"].replay()
         self.replays += 1
         loss, acc = ent["loss"].clone(), ent["acc"].clone()            # the graph's output tensors are overwritten by the next replay
+        end_episode(task_dict)                                         # (the eager paths end theirs in train_task)
         return loss, acc, {"accuracy": acc}
 
     def _generic(self, task_dict):
@@ -706,7 +712,7 @@ class GraphedEpisode:
                 return self._eager(task_dict)
             static = {k: v.detach().to(cfg.device).clone() if k in self.KEYS else v for k, v in task_dict.items()}
             ent = self._capture(static, ("generic",) + shapes)
-            return self._replay(ent)
+            return self._replay(ent, task_dict)
         if tuple(plan.counts) != ent["counts"] or plan.classes != ent["plan"].classes:
             return self._eager(task_dict)
         for k in self.KEYS:
@@ -714,7 +720,7 @@ class GraphedEpisode:
         ent["plan"]._packed.copy_(plan._packed)      # class ids, row map and its full-row-map views in one device copy
         # prepare_task's derived tensor (target labels as int64) lives in the static `prepared` tuple
         ent["prepared"][5].copy_(ent["task"]["target_labels"][0].long())
-        return self._replay(ent)
+        return self._replay(ent, task_dict)
 
     # ---- several episodes per graph.  A one-episode graph must join the weight-gradient stream before it ends, so its ~4 ms tail no
     # longer runs under the next episode's forward (the replay loop is ~5 % slower than the eager loop on the GPU side).  The episodes
@@ -793,7 +799,7 @@ class GraphedEpisode:
             del self.graphs[key]
             self.seen.discard(key)
             return self._generic(task_dict)
-        return self._replay(ent)
+        return self._replay(ent, task_dict)
 
 
 def save_checkpoint(student, iteration, config, bn_stats=None):
@@ -884,9 +890,8 @@ def _train_loop(student, teacher, video_loader, distiller, optimizer, scheduler,
             if r is not None:
                 losses.append(r[0])
                 accuracies.append(r[1])
-    for task_dict in video_loader:
-        if iteration >= total_iterations:
-            break
+    # (islice: no episode is drawn that the loop does not run - a StreamedEpisodes loader would never get its input set back)
+    for task_dict in itertools.islice(video_loader, total_iterations - iteration):
         iteration += 1
         torch.set_grad_enabled(True)
         if (((iteration + 1) % every == 0) or (iteration == (total_iterations - 1))) and hasattr(optimizer, "expect_step"):
@@ -934,6 +939,7 @@ def test_task(task_dict, model, accuracy_fn, config):
         acc = accuracy_fn(logits["kl"], target_labels)
     else:
         acc = accuracy_fn(logits, target_labels)
+    end_episode(task_dict, train=False)
     return {"test_accuracy": acc}
 
 
@@ -944,11 +950,7 @@ def test(model, video_loader, accuracy_fn, config):
     with torch.no_grad():
         if hasattr(video_loader, "dataset"):
             video_loader.dataset.train = False
-        iteration = 0
-        for task_dict in video_loader:
-            if iteration >= config.num_test_tasks:
-                break
-            iteration += 1
+        for task_dict in itertools.islice(video_loader, config.num_test_tasks):      # (as in train: no episode drawn and left unscored)
             accuracies.append(test_task(task_dict, model, accuracy_fn, config)["test_accuracy"].item())
         if hasattr(video_loader, "dataset"):
             video_loader.dataset.train = True

@@ -514,6 +514,60 @@ def test_range_fence_takes_the_three_plane_form(dev):
     ops.h2_fence_reset()
 
 
+def test_range_fence_judges_each_lane_on_its_own(dev, monkeypatch):
+    """the range fence in the pipelined loop (trainloop.PipelinedEpisodes: the forward of episode i + 1, on the other lane, is queued before
+    the backward of episode i).  A stand-in student writes the outlier tensor of test_range_fence_takes_the_three_plane_form at one site in
+    every episode.  The h2_fence_step() of _backward(i) judges episode i's entries only - the other lane's stay pending, their producers
+    need not have run - and, each lane comparing against its own previous episode, the outlier is flagged when episode 2 (the second of
+    lane 0) is judged, on every run."""
+    from types import SimpleNamespace
+    from litemkd_amd import ops, trainloop as TL
+    g = torch.Generator(device=dev).manual_seed(11)
+    N, H, C = 4, 14, 64
+    outlier = torch.relu(torch.randn(N, H, H, C, device=dev, generator=g))
+    outlier[0, 7, 7, 0] = 2.0 ** 20
+    st = _identity_table(C, dev)
+    site = ("y", 1)
+
+    class Student(torch.nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.w = torch.nn.Parameter(torch.ones((), device=dev))
+
+        def forward(self, context_images, context_labels, target_images):
+            ops.bn_apply(outlier, st, False, site=site)      # this episode's producer, on its lane's stream
+            return {"logits": self.w * target_images.sum()}
+
+    class Teacher(torch.nn.Module):
+        def forward(self, context_features, context_labels, target_features):
+            return {"logits": target_features.sum()}
+
+    x, labels = torch.rand(1, 5, 8, device=dev), torch.arange(5, device=dev).float().unsqueeze(0)
+    ep = {"support_set": x, "target_set": x, "support_set_feature_teacher": x, "target_set_feature_teacher": x,
+          "support_labels": labels, "target_labels": labels}
+    cfg = SimpleNamespace(device=dev, way=5, distill_name="plain")
+    distiller = SimpleNamespace(plain=lambda logits, teacher_logits, target_labels: {"loss": logits})
+    judged = []
+    step = ops.h2_fence_step
+
+    def spy(wait=False):
+        before = sorted({e[1] for e in ops._FENCE_PENDING})
+        step(wait=True)      # (this call's verdicts are taken in at once: a flag belongs to the episode judged here)
+        judged.append((ops.LANE[0], before, sorted({e[1] for e in ops._FENCE_PENDING}), ops.h2_fence_flagged()))
+    monkeypatch.setattr(ops, "h2_fence_step", spy)
+    for run in range(3):
+        ops.h2_fence_reset()
+        del judged[:]
+        pipe = TL.PipelinedEpisodes(Student(), Teacher(), distiller, lambda logits, target_labels: logits.detach(), cfg, depth=1)
+        for _ in range(5):
+            pipe.push(ep)
+        pipe.flush()
+        torch.cuda.synchronize()
+        assert [j[:3] for j in judged] == [(0, [0, 1], [1]), (1, [0, 1], [0]), (0, [0, 1], [1]), (1, [0, 1], [0]), (0, [0], [])], (run, judged)
+        assert [j[3] for j in judged] == [[], [], [site], [site], [site]], (run, judged)
+    ops.h2_fence_reset()
+
+
 @pytest.mark.parametrize("frames,H,seg", [(37, 56, 0), (64, 56, 23), (400, 14, 0), (5, 7, 2)])
 def test_persistent_layer1_kernel_equals_one_workgroup_per_tile(dev, frames, H, seg):
     """round 5: the two-plane launches with Cout <= 64 run conv_patch_x3_kernel<.., 3, ..> (v_mfma_f32_32x32x16_f16) with PERSISTENT workgroups -

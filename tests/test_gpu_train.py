@@ -449,7 +449,7 @@ class _HostEpisodes:
 def test_streamed_loader_equals_resident_inputs(dev):
     """trainloop.StreamedEpisodes (the loader inside the product loop, under the schedule that is timed): a
     prefetch thread hands over pinned host episodes, a copy stream uploads the uint8 frames + features and runs the frame transform into
-    one of three static input sets, the pipelined loop (Schedule.bench) consumes them and releases each set to the copy stream through
+    one of four static input sets, the pipelined loop (Schedule.bench) consumes them and releases each set to the copy stream through
     events.  Seven episodes with optimizer steps: losses, accuracies and the weights are BIT-identical to the same loop fed with the same
     episodes transformed up front on the compute stream (resident inputs)."""
     from litemkd_amd import trainloop as TL
@@ -481,7 +481,7 @@ def test_streamed_loader_equals_resident_inputs(dev):
             losses, accs = TL.train(student, teacher, loader, distiller, opt, sch, acc_fn, cfg, schedule=sched)
             torch.cuda.synchronize()
             if streamed:
-                assert loader.staged == n and all(s is not None for s in loader.sets)      # three sets, each staged more than once
+                assert loader.staged == n and all(s is not None for s in loader.sets)      # four sets, each staged at least once
                 loader.close()
         return losses, accs, opt.bucket.flat.clone()
     l_r, a_r, w_r = run(False)
@@ -490,10 +490,100 @@ def test_streamed_loader_equals_resident_inputs(dev):
     assert torch.equal(w_s, w_r)
 
 
+class _TwoModeEpisodes:
+    """a host-side episode source whose query count follows dataset.train, as the reference's VideoDataset does: query_per_class
+    queries in training, query_per_class_test in test(); pageable tensors (StreamedEpisodes copies them into its pinned ring)"""
+
+    def __init__(self, cfg):
+        from litemkd_amd.video_transform import GpuFrameTransform
+        self.cfg, self.train, self.dataset, self.n = cfg, True, self, 0
+        self.tf = GpuFrameTransform(cfg.img_size, "cpu")
+
+    def host_episode(self):
+        c, train = self.cfg, self.train
+        g = torch.Generator().manual_seed(self.n)
+        self.n += 1
+        q = c.query_per_class if train else c.query_per_class_test
+        ns, nq = c.way * c.shot, c.way * q
+        return {"frames": torch.randint(0, 256, ((ns + nq) * c.seq_len, 100, 132, 3), dtype=torch.uint8, generator=g),
+                "params": [self.tf.draw(100, 132, train) for _ in range(ns + nq)],
+                "features": torch.randn(ns + nq, c.seq_len, 2048, generator=g), "ns": ns,
+                "support_labels": torch.arange(c.way).repeat_interleave(c.shot)[torch.randperm(ns, generator=g)].float(),
+                "target_labels": torch.arange(c.way).repeat_interleave(q)[torch.randperm(nq, generator=g)].float()}
+
+
+def test_streamed_sets_are_released_across_a_mid_training_test(dev):
+    """StreamedEpisodes under train() with a test_iters entry inside the run (Schedule.bench, fp32h2; 84 px, the smallest size the frame
+    transform has): test() switches the source to test mode, whose episodes have another query count.  Every test episode has the
+    test-mode shape and training resumes on train-mode shapes; every episode handed out is released exactly once (trainloop.end_episode:
+    PipelinedEpisodes and test_task), staging never meets a busy set (it would raise), none is busy after close(); the weights are finite."""
+    from litemkd_amd import trainloop as TL
+    from litemkd_amd.options import default_args
+    from litemkd_amd.schedule import Schedule
+    cfg = default_args(shot=1, query_per_class=2, query_per_class_test=1, img_size=84, trans_dropout=0.1, device=dev, learning_rate=1e-2,
+                       training_iterations=8, tasks_per_batch=2, test_iters=[4], num_test_tasks=3, print_freq=10 ** 9, save_freq=10 ** 9)
+    seen, released = [], []
+    orig = TL.prepare_task
+
+    def spy(task_dict, device, images_to_device=True):
+        seen.append((torch.is_grad_enabled(), task_dict["target_set"].shape[1]))
+        return orig(task_dict, device, images_to_device)
+    sched = Schedule.bench(conv_dtype="fp32h2")
+    TL.prepare_task = spy
+    try:
+        with sched.applied():
+            torch.manual_seed(0)
+            student, teacher, _, distiller, acc_fn, _, opt, sch = TL.make(cfg)
+            loader = TL.StreamedEpisodes(_TwoModeEpisodes(cfg), cfg, dev)
+            release = loader.release
+            loader.release = lambda k: (released.append(k), release(k))
+            losses, _ = TL.train(student, teacher, loader, distiller, opt, sch, acc_fn, cfg, schedule=sched)
+            torch.cuda.synchronize()
+            loader.close()
+    finally:
+        TL.prepare_task = orig
+    L = cfg.seq_len
+    assert len(losses) == 8
+    assert seen == [(True, 5 * 2 * L)] * 3 + [(False, 5 * 1 * L)] * 3 + [(True, 5 * 2 * L)] * 5, seen      # test() after the third episode
+    assert len(released) == len(seen) and set(released) == set(range(loader.nsets)), released
+    assert not any(s["busy"] for s in loader.sets if s is not None)
+    assert bool(torch.isfinite(opt.bucket.flat).all())
+
+
+def test_streamed_loader_refuses_a_busy_set(dev, monkeypatch):
+    """StreamedEpisodes' input-set ownership: asked for 2 sets under PIPELINE_DEPTH = 2 it keeps PIPELINE_DEPTH + 2 = 4.  A consumer that
+    never releases its episodes makes the staging of the fifth - into set 0 again - raise; one that ends every episode
+    (trainloop.end_episode) runs through all of them and leaves no set busy."""
+    from litemkd_amd import trainloop as TL
+    from litemkd_amd.options import default_args
+    cfg = default_args(shot=1, query_per_class=1, img_size=84, device=dev)
+    monkeypatch.setattr(TL, "PIPELINE_DEPTH", 2)
+    loader = TL.StreamedEpisodes(_HostEpisodes(cfg, 8), cfg, dev, sets=2)
+    assert loader.nsets == 4
+    it = iter(loader)
+    try:
+        for _ in range(3):
+            next(it)      # episode i handed out, i + 1 staged: after the third, sets 0 - 3 are busy
+        with pytest.raises(RuntimeError, match="input set 0 of 4 is still busy.*PIPELINE_DEPTH = 2 needs 4 sets"):
+            next(it)
+    finally:
+        del it
+        loader.close()
+    loader = TL.StreamedEpisodes(_HostEpisodes(cfg, 8), cfg, dev, sets=2)
+    n = 0
+    for td in loader:
+        TL.end_episode(td, train=False)
+        n += 1
+    torch.cuda.synchronize()
+    loader.close()
+    assert n == 8 and loader.staged == 8 and not any(s["busy"] for s in loader.sets)
+
+
 def test_stream_lifetime_audit_finds_nothing(dev):
     """lite-mkd_amd/_audit.py: every entry-point call of seven 64-px training episodes with optimizer steps under
     Schedule.bench() and Schedule.two_call() in fp32h2, with each tensor argument checked - a tensor used on a stream other than the one it
-    was allocated on must carry a record_stream for that stream (or a declared reason).  In a process of its own: the audit wraps torch's
+    was allocated on must carry a record_stream for that stream (or a declared reason).  The Schedule.bench() run's episodes come through
+    StreamedEpisodes (at 84 px, the frame transform's smallest size), so its static input sets are checked too.  In a process of its own: the audit wraps torch's
     allocation functions at import."""
     import os
     import subprocess
