@@ -428,6 +428,42 @@ int lmkd_stem_unpool_bn_bwd_seg(const float* dy, const unsigned char* idx, const
                                 float* dgamma, float* dbeta, int accumulate_param_grads, int N, int N0, int H, int W, int C, void* stream,
                                 const lmkd_amax_desc* amax /*nullable*/);
 
+/* ---- STRM student family (model/backbone/strm18_student.py, strmbackbone.py, model/classifiers/strm_res18_sup.py); csrc/strm.hip.
+ * fp32 tensors, fixed-order reductions, no float atomics. */
+/* strm18_student.py:236-246 + Self_Attn_Bot.pe (:131-132): AdaptiveMaxPool2d((4,4)) of x [F,H,W,C] with the 16 patches kept,
+   y [F,16,C] = (max + pe [16,C]) * mask (nullable, [F,16,C]); idx [F,16,C] = h * W + w of the first maximum in row-major window order
+   (torch's return_indices; H * W <= 256).  Backward gathers over the windows that hold a pixel: dx = sum [idx == pixel] dy * mask. */
+int lmkd_strm_patchpool_fwd(const float* x, const float* pe, const float* mask, float* y, unsigned char* idx, int F, int H, int W, int C,
+                            void* stream);
+int lmkd_strm_patchpool_bwd(const float* dy, const float* mask, const unsigned char* idx, float* dx, int F, int H, int W, int C, void* stream);
+/* Self_Attn_Bot.forward (:134-166) after the projections: qkv [F,16,3C] = query | key | value rows (one GEMM over the concatenated
+   weights), probs [F,16,16] = softmax(Q K^T) (unscaled), y [F,16,C] = gamma[0] * (probs V) + x; C % 256 == 0.  Backward: dqkv [F,16,3C]
+   = dQ | dK | dV, dgamma[0] = sum dy * (probs V) through dgamma_part [F] (per frame, then one fixed-order reduction); the residual's
+   input gradient is dy itself. */
+int lmkd_strm_attn_fwd(const float* x, const float* qkv, const float* gamma, float* y, float* probs, int F, int C, void* stream);
+int lmkd_strm_attn_bwd(const float* dy, const float* qkv, const float* probs, const float* gamma, float* dqkv, float* dgamma_part,
+                       float* dgamma, int F, int C, void* stream);
+/* MLP_Mix_Enrich.forward (:185-202) up to residual2: xp [V,L,D] = (x + pe [L,D]) * mask (nullable), y = W2 relu(W1 xp + b1) + b2 + xp
+   along the frame axis (W1, W2 [L,L], L == 8); hmask (nullable) [V,L,D] = 1 where hidden unit k of (video, channel) is active.  Backward: dx, dparams [144] = dW1 | db1 | dW2 | db2 through part
+   [lmkd_strm_tokmlp_parts(V, D)][144] per-workgroup partial rows. */
+long lmkd_strm_tokmlp_parts(long V, int D);
+int lmkd_strm_tokmlp_fwd(const float* x, const float* pe, const float* mask, const float* w1, const float* b1, const float* w2, const float* b2,
+                         float* xp, float* y, unsigned char* hmask, int V, int L, int D, void* stream);
+int lmkd_strm_tokmlp_bwd(const float* dy, const float* xp, const float* mask, const float* w1, const float* b1, const float* w2, float* dx,
+                         float* part, float* dparams, int V, int L, int D, void* stream);
+/* DistanceLoss.forward (strm_res18_sup.py:188-243).  P [NV * L][2 Hd]: every frame through both halves of clsW (first-frame columns |
+   second-frame columns); E [NV * T][Hd] = relu(P_a[i] + P_b[j] + bias) for the T = L (L - 1) / 2 frame pairs in combinations order. */
+int lmkd_strm_pair_embed(const float* P, const float* bias, float* E, int NV, int L, int Hd, void* stream);
+/* rows of E: Ns support videos, then Nq query videos.  order [Ns]: support video of class-sorted position c * shot + m.  dist / idx
+   [Nq * T][way]: minimum over the class's shot * T rows of sqrt(sum (q - s)^2) and its row m * T + t (first smallest);
+   logits [Nq][way] = - mean over the T pair rows.  Hd == 1024. */
+int lmkd_strm_patchdist_fwd(const float* E, const int* order, float* dist, int* idx, float* logits, int Ns, int Nq, int way, int shot, int L,
+                            int Hd, void* stream);
+/* g [Nq][way], pos [Ns] = class-sorted position of each support video -> dpre [NV * T][Hd] (gradient before the ReLU) and
+   dP [NV * L][2 Hd]; distance 0 gives gradient 0 */
+int lmkd_strm_patchdist_bwd(const float* E, const int* order, const int* pos, const float* dist, const int* idx, const float* g, float* dpre,
+                            float* dP, int Ns, int Nq, int way, int shot, int L, int Hd, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

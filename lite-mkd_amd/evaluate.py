@@ -58,7 +58,10 @@ class Evaluator:
                 else:
                     model_dict = self.model(context_teacher_feature, context_labels, target_teacher_feature)
                 logits = model_dict["logits"]
-                if isinstance(logits, dict):         # two-head students: kl + ce as in the training loop (trainwandb.py:247-257)
+                strm_logits = TL.strm_accuracy_logits(getattr(self.args, "distill_name", None), logits)
+                if strm_logits is not None:         # STRM students: 0.2 * pat + fr1 + fr2 / 0.1 * pat + fr (test.py / trainwandb.py:305-337)
+                    logits = strm_logits
+                elif isinstance(logits, dict):         # two-head students: kl + ce as in the training loop (trainwandb.py:247-257)
                     logits = logits["kl"] + logits["ce"] if "ce" in logits else logits["kl"]
                 accuracy = self.accuracy_fn(logits.to(self.device), target_labels)
                 self.log("For Task: %s,  Testing Accuracy is %s" % (self.args.mode, accuracy.item()))
@@ -73,7 +76,7 @@ def main(argv=None):
     import argparse
     ap = argparse.ArgumentParser()
     base = default_args()
-    for k in ("test_model", "test_model_path", "teacher_checkpoint", "model_backbone", "model_classifier", "dataset", "mode"):
+    for k in ("test_model", "test_model_path", "teacher_checkpoint", "model_backbone", "model_classifier", "distill_name", "dataset", "mode"):
         ap.add_argument("--" + k, default=getattr(base, k))
     for k in ("num_test_tasks", "way", "shot", "query_per_class_test", "seq_len", "img_size"):
         ap.add_argument("--" + k, type=int, default=getattr(base, k))

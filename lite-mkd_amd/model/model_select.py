@@ -7,7 +7,8 @@ import torch.nn as nn
 
 from .. import ops
 from . import classifiers
-from .backbone import mobile_large, mobile_large_2fc, resnet18_2fc, resnet18_student, resnet50_2fc, resnet50_stduent
+from .backbone import (mobile_large, mobile_large_2fc, resnet18_2fc, resnet18_student, resnet50_2fc, resnet50_stduent, strm18_student,
+                       strmbackbone)
 
 # every key of the reference's name2backbone (model_select.py:167-180); None = plugin outside the hot path
 name2backbone = {
@@ -21,6 +22,21 @@ name2backbone = {
     "meta_baseline_fc2": None,
     "moblienetv3_fc2": mobile_large_2fc,
     "moblienetv3": mobile_large,
+}
+
+# The STRM backbones live in a second map: their entries in name2backbone stay None (those entries are pinned by the registry tests),
+# and select_model_student consults this map when name2backbone[name] is None.  An STRM backbone returns feature dicts
+# ({'distance', 'trx1', 'trx2'} / {'distance', 'trx'}) that only the STRM classifiers read - in the reference any other pairing dies in a
+# TypeError inside the classifier - so here the pairing of an STRM backbone with another classifier, and of an STRM classifier with
+# another backbone, raises NotImplementedError naming both plugins.
+name2strm_backbone = {
+    "strm18_student": strm18_student,
+    "strmbackbone": strmbackbone,
+}
+# classifier names each STRM backbone can feed (the feature keys they read)
+strm_pairings = {
+    "strm18_student": ("strm_res18_sup",),
+    "strmbackbone": ("strmclassifiers", "strm_res18"),
 }
 
 # model_select.py:182-199
@@ -52,6 +68,15 @@ def _classifier_class(classifiername):
 def select_model_student(args):
     """model_select.py:161-209.  Unknown names raise KeyError like the reference."""
     backbone_cls = name2backbone[args.model_backbone]
+    strm_classifiers = {c for cs in strm_pairings.values() for c in cs}
+    if backbone_cls is None and args.model_backbone in name2strm_backbone:
+        if args.model_classifier not in strm_pairings[args.model_backbone]:
+            raise NotImplementedError("backbone plugin '%s' returns STRM feature dicts that classifier plugin '%s' cannot read (it pairs with %s)"
+                                      % (args.model_backbone, args.model_classifier, " / ".join(strm_pairings[args.model_backbone])))
+        backbone_cls = name2strm_backbone[args.model_backbone]
+    elif backbone_cls is not None and args.model_classifier in strm_classifiers:
+        raise NotImplementedError("classifier plugin '%s' reads STRM feature dicts that backbone plugin '%s' does not return"
+                                  % (args.model_classifier, args.model_backbone))
     if backbone_cls is None:
         raise NotImplementedError("backbone plugin '%s' is outside the MI355X hot path (SURVEY.md 8f N1)" % args.model_backbone)
     backbone = backbone_cls(args)

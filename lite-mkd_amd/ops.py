@@ -2037,10 +2037,12 @@ class ClassPlan:
         self.device = dev
         # one upload: [cls | rowmap | identity tail]: rowmap followed by the tail IS full_rowmap() for any query count up to `tail`
         tail = max(64, 2 * self.ns) if nq_hint is None else int(nq_hint)
-        packed = torch.tensor(vals + pos + list(range(self.ns, self.ns + tail)), dtype=torch.int32)
+        # (the class-sorted order rides at the end of the same upload: order[p] = support video at class-sorted position p, for PatchDistFn)
+        packed = torch.tensor(vals + pos + list(range(self.ns, self.ns + tail)) + order, dtype=torch.int32)
         self._packed = h2d_async(packed, dev)
         self.cls = self._packed[:self.ns]
         self.rowmap = self._packed[self.ns:2 * self.ns]
+        self.order = self._packed[2 * self.ns + tail:]
         self._tail = tail
         self.uniform = len(set(self.counts)) == 1
         self._full = {}
@@ -2793,3 +2795,339 @@ class MnvSEFn(torch.autograd.Function):
         da = torch.empty_like(a)
         lib().call("lmkd_se_scale_bwd", _p(dy), _p(a), _p(s), _p(dm), _p(da), None, N, HW, C, _stream())
         return da, dw1, db1, dw2, db2
+
+
+# ------------------------------------------------------------------------------------------
+# STRM student family (model/backbone/strm18_student.py, strmbackbone.py, model/classifiers/strm_res18_sup.py; csrc/strm.hip)
+# ------------------------------------------------------------------------------------------
+STRM_PATCHES = 16
+# tests: a dict here collects the selections an episode made - "pool": the arg-max bytes of every PatchPoolFn call in call order,
+# "dist": the arg-min rows of every PatchDistFn call, "relu": the ReLU masks of the head in call order (bottleneck MLPs, token MLP
+# [V,8,D], pair embedding), "dropout": the three dropout masks (attn_pat.pe, fr_enrich.pe, DistanceLoss) - so that a reference evaluation can run
+# on the same selections and masks (as BLOCK_TAPS for the trunk)
+STRM_TAPS = None
+
+
+def _strm_chk(*tensors):
+    if _ACT_DTYPE[0] is not torch.float32:
+        raise RuntimeError("the STRM backbones run fp32 activations only; set_activation_dtype('%s') is not supported for them"
+                           % get_activation_dtype())
+    _chk(*tensors)
+
+
+def strm_patchpool_fwd(x, pe, mask=None):
+    """x [F,H,W,C] NHWC -> (y [F,16,C] = (AdaptiveMaxPool2d((4,4))(x) + pe) * mask, idx uint8 [F,16,C] = h * W + w of the maximum)"""
+    _strm_chk(x, pe, mask)
+    F_, H, W, C = x.shape
+    y = _empty((F_, STRM_PATCHES, C), x)
+    idx = torch.empty((F_, STRM_PATCHES, C), dtype=torch.uint8, device=x.device)
+    lib().call("lmkd_strm_patchpool_fwd", _p(x), _p(pe), _p(mask), _p(y), _p(idx), F_, H, W, C, _stream())
+    return y, idx
+
+
+def strm_patchpool_bwd(dy, mask, idx, H, W):
+    """gradient of strm_patchpool_fwd's input from dy [F,16,C] and the stored selections"""
+    _strm_chk(dy, mask, idx)
+    F_, _, C = dy.shape
+    dx = _empty((F_, H, W, C), dy)
+    lib().call("lmkd_strm_patchpool_bwd", _p(dy), _p(mask), _p(idx), _p(dx), F_, H, W, C, _stream())
+    return dx
+
+
+class PatchPoolFn(torch.autograd.Function):
+    """strm18_student.py:236-246 + the table add and dropout of Self_Attn_Bot.pe (:131-132): NHWC trunk output -> [F,16,C] patches"""
+
+    @staticmethod
+    def forward(ctx, x, pe, mask):
+        x = x.contiguous()
+        y, idx = strm_patchpool_fwd(x, pe, mask)
+        if STRM_TAPS is not None:
+            STRM_TAPS.setdefault("pool", []).append(idx)
+        ctx.save_for_backward(idx, mask)
+        ctx.hw = (x.shape[1], x.shape[2])
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        _audit.engine_owned(dy)
+        idx, mask = ctx.saved_tensors
+        return strm_patchpool_bwd(dy.contiguous(), mask, idx, *ctx.hw), None, None
+
+
+def strm_attn_fwd(x, qkv, gamma):
+    """x [F,16,C], qkv [F,16,3C] -> (y = gamma * softmax(Q K^T) V + x, probs [F,16,16])"""
+    _strm_chk(x, qkv, gamma)
+    F_, NP, C = x.shape
+    if NP != STRM_PATCHES or tuple(qkv.shape) != (F_, NP, 3 * C):
+        raise RuntimeError("strm_attn_fwd expects x [F,16,C] and qkv [F,16,3C]")
+    y = torch.empty_like(x)
+    probs = _empty((F_, NP, NP), x)
+    lib().call("lmkd_strm_attn_fwd", _p(x), _p(qkv), _p(gamma), _p(y), _p(probs), F_, C, _stream())
+    return y, probs
+
+
+def strm_attn_bwd(dy, qkv, probs, gamma):
+    """-> (dqkv [F,16,3C], dgamma [1]); the residual's input gradient is dy"""
+    _strm_chk(dy, qkv, probs, gamma)
+    F_, NP, C = dy.shape
+    dqkv = torch.empty_like(qkv)
+    part = _empty((F_,), dy)
+    dgamma = _empty((1,), dy)
+    lib().call("lmkd_strm_attn_bwd", _p(dy), _p(qkv), _p(probs), _p(gamma), _p(dqkv), _p(part), _p(dgamma), F_, C, _stream())
+    return dqkv, dgamma
+
+
+class PatchAttnFn(torch.autograd.Function):
+    """Self_Attn_Bot.forward (strm18_student.py:134-163) on the table-added patches: the three projections as ONE GEMM over the
+    concatenated weights, then energy / softmax / attn V / gamma * out + x per frame in one launch"""
+
+    @staticmethod
+    def forward(ctx, x, wq, bq, wk, bk, wv, bv, gamma):
+        x = x.contiguous()
+        F_, NP, C = x.shape
+        wcat = torch.cat([wq, wk, wv], 0)
+        bcat = torch.cat([bq, bk, bv], 0)
+        _strm_chk(x, wcat, bcat, gamma)
+        qkv = _empty((F_, NP, 3 * C), x)
+        gemm("K", "K", F_ * NP, 3 * C, C, x, C, wcat, C, qkv, 3 * C, bias=bcat)
+        y, probs = strm_attn_fwd(x, qkv, gamma)
+        ctx.save_for_backward(x, wcat, qkv, probs, gamma)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        _audit.engine_owned(dy)
+        x, wcat, qkv, probs, gamma = ctx.saved_tensors
+        dy = dy.contiguous()
+        F_, NP, C = x.shape
+        M = F_ * NP
+        dqkv, dgamma = strm_attn_bwd(dy, qkv, probs, gamma)
+        dw = _empty((3 * C, C), x)
+        gemm("M", "N", 3 * C, C, M, dqkv, 3 * C, x, C, dw, C)            # d[Wq; Wk; Wv] = dqkv^T @ x
+        db = colsum(dqkv.view(M, 3 * C))
+        dx = dy.clone()
+        gemm("K", "N", M, C, 3 * C, dqkv, 3 * C, wcat, C, dx, C, beta=1.0)      # dx = dy + dqkv @ [Wq; Wk; Wv]
+        return dx, dw[:C], db[:C], dw[C:2 * C], db[C:2 * C], dw[2 * C:], db[2 * C:], dgamma
+
+
+GEMM_ROW_TILE = 64      # lmkd_gemm_f32 rounds a row's dot product according to the row's position inside its 64-row tile
+
+
+def _row_segments(M, seg):
+    """row ranges to launch a row-wise GEMM over: the whole range when the second trunk call's rows start on a tile boundary, else one
+    launch per call - then every row sits where it would in the reference's two separate calls and the result is bit-identical to them
+    (measured: 1 ulp differences in res18_2048's output otherwise, tests/test_gpu_strm.py::test_one_call_head_equals_two_calls)"""
+    if not seg or seg >= M or seg % GEMM_ROW_TILE == 0:
+        return [(0, M)]
+    return [(0, seg), (seg, M - seg)]
+
+
+class LinearXFn(torch.autograd.Function):
+    """y = relu?(x W^T + b) (+ res): nn.Linear with the ReLU in the GEMM's epilogue or the residual in its beta = 1 accumulate
+    (Bottleneck_Perceptron_3_layer_res / Bottleneck_Perceptron_2_layer, res18_2048, fc1 / fc2: strm18_student.py:65-99,258-276).
+    seg: rows [0, seg) come from the support frames, the rest from the query frames (_row_segments)."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, relu, res, seg=0):
+        x = x.contiguous()
+        w = w.contiguous()
+        _strm_chk(x, w, b, res)
+        if relu and res is not None:
+            raise RuntimeError("LinearXFn: ReLU and residual together are not used by any STRM layer")
+        M, K = x.shape
+        N = w.shape[0]
+        y = res.contiguous().clone() if res is not None else _empty((M, N), x)
+        for r0, rows in _row_segments(M, seg):
+            gemm("K", "K", rows, N, K, x, K, w, K, y, N, beta=1.0 if res is not None else 0.0, bias=b, relu=relu, A_off=r0 * K, C_off=r0 * N)
+        if relu and STRM_TAPS is not None:
+            STRM_TAPS.setdefault("relu", []).append(y > 0)
+        ctx.save_for_backward(x, w, y if relu else None)
+        ctx.has_res, ctx.seg = res is not None, seg
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        _audit.engine_owned(dy)
+        x, w, y = ctx.saved_tensors
+        dy = dy.contiguous()
+        M, K = x.shape
+        N = w.shape[0]
+        g = dy
+        if y is not None:
+            g = _empty((M, N), x)
+            lib().call("lmkd_relu_backward", _p(dy), _p(y), _p(g), M * N, _stream())
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            dx = _empty((M, K), x)
+            for r0, rows in _row_segments(M, ctx.seg):
+                gemm("K", "N", rows, K, N, g, N, w, K, dx, K, A_off=r0 * N, C_off=r0 * K)
+        if ctx.needs_input_grad[1]:
+            dw = _empty((N, K), x)
+            gemm("M", "N", N, K, M, g, N, x, K, dw, K)
+        if ctx.needs_input_grad[2]:
+            db = colsum(g)
+        return dx, dw, db, None, (dy if ctx.has_res else None), None
+
+
+class PatchMeanFn(torch.autograd.Function):
+    """torch.mean over the 16 patches (strm18_student.py:254-255): [F,16,C] -> [F,C]"""
+
+    @staticmethod
+    def forward(ctx, x):
+        x = x.contiguous()
+        _strm_chk(x)
+        F_, NP, C = x.shape
+        y = _empty((F_, C), x)
+        lib().call("lmkd_mean_frames", _p(x), _p(y), F_, NP, C, _stream())
+        ctx.shape = (F_, NP, C)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        _audit.engine_owned(dy)
+        F_, NP, C = ctx.shape
+        dx = _empty((F_, NP, C), dy)
+        lib().call("lmkd_mean_frames_bwd", _p(dy.contiguous()), _p(dx), F_, NP, C, _stream())
+        return dx
+
+
+def strm_tokmlp_fwd(x, pe, mask, w1, b1, w2, b2):
+    """x [V,8,D] -> (xp = (x + pe) * mask, y = W2 relu(W1 xp + b1) + b2 + xp along the frame axis)"""
+    _strm_chk(x, pe, mask, w1, b1, w2, b2)
+    V, L, D = x.shape
+    xp, y = torch.empty_like(x), torch.empty_like(x)
+    hmask = torch.empty(x.shape, dtype=torch.uint8, device=x.device) if STRM_TAPS is not None else None
+    lib().call("lmkd_strm_tokmlp_fwd", _p(x), _p(pe), _p(mask), _p(w1), _p(b1), _p(w2), _p(b2), _p(xp), _p(y), _p(hmask), V, L, D, _stream())
+    if hmask is not None:
+        STRM_TAPS.setdefault("relu", []).append(hmask)
+    return xp, y
+
+
+def strm_tokmlp_bwd(dy, xp, mask, w1, b1, w2):
+    """-> (dx, dW1 [8,8], db1 [8], dW2 [8,8], db2 [8])"""
+    _strm_chk(dy, xp, mask, w1, b1, w2)
+    V, L, D = dy.shape
+    dx = torch.empty_like(dy)
+    part = _empty((lib().value("lmkd_strm_tokmlp_parts", V, D), 2 * L * L + 2 * L), dy)
+    dp = _empty((2 * L * L + 2 * L,), dy)
+    lib().call("lmkd_strm_tokmlp_bwd", _p(dy), _p(xp), _p(mask), _p(w1), _p(b1), _p(w2), _p(dx), _p(part), _p(dp), V, L, D, _stream())
+    n = L * L
+    return dx, dp[:n].view(L, L), dp[n:n + L], dp[n + L:2 * n + L].view(L, L), dp[2 * n + L:]
+
+
+class TokenMLPFn(torch.autograd.Function):
+    """MLP_Mix_Enrich.forward up to residual2 (strm18_student.py:185-196): table add + dropout, Token_Perceptron over the frames, residual"""
+
+    @staticmethod
+    def forward(ctx, x, pe, mask, w1, b1, w2, b2):
+        x = x.contiguous()
+        w1, w2 = w1.contiguous(), w2.contiguous()
+        xp, y = strm_tokmlp_fwd(x, pe, mask, w1, b1, w2, b2)
+        ctx.save_for_backward(xp, mask, w1, b1, w2)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        _audit.engine_owned(dy)
+        xp, mask, w1, b1, w2 = ctx.saved_tensors
+        dx, dw1, db1, dw2, db2 = strm_tokmlp_bwd(dy.contiguous(), xp, mask, w1, b1, w2)
+        return dx, None, None, dw1, db1, dw2, db2
+
+
+def _strm_plan_check(plan, Ns):
+    if not plan.uniform or len(plan.classes) != plan.way or plan.ns != Ns:
+        raise NotImplementedError("the patch-distance head needs every one of the %d classes with the same number of support videos "
+                                  "(got %s)" % (plan.way, plan.counts))
+    return plan.counts[0]
+
+
+def strm_patchdist_embed(X, w, b, L):
+    """X [NV*L, Din] frame features, clsW weight [Hd, 2 Din] -> (P [NV*L, 2 Hd] per-frame projections through both halves of clsW,
+    E [NV*T, Hd] = relu(P_a[i] + P_b[j] + b) per frame pair)"""
+    _strm_chk(X, w, b)
+    M, Din = X.shape
+    Hd = w.shape[0]
+    P = _empty((M, 2 * Hd), X)
+    gemm("K", "K", M, Hd, Din, X, Din, w, 2 * Din, P, 2 * Hd)
+    gemm("K", "K", M, Hd, Din, X, Din, w, 2 * Din, P, 2 * Hd, B_off=Din, C_off=Hd)
+    NV = M // L
+    E = _empty((NV * (L * (L - 1) // 2), Hd), X)
+    lib().call("lmkd_strm_pair_embed", _p(P), _p(b), _p(E), NV, L, Hd, _stream())
+    if STRM_TAPS is not None:
+        STRM_TAPS.setdefault("relu", []).append(E > 0)
+    return P, E
+
+
+def strm_patchdist_fwd(E, plan, Ns, Nq, L):
+    """-> (logits [Nq, way], dist [Nq*T, way], idx int32 [Nq*T, way]: row member * T + t of the nearest support pair row per class)"""
+    shot = _strm_plan_check(plan, Ns)
+    T = L * (L - 1) // 2
+    dist = _empty((Nq * T, plan.way), E)
+    idx = torch.empty((Nq * T, plan.way), dtype=torch.int32, device=E.device)
+    logits = _empty((Nq, plan.way), E)
+    lib().call("lmkd_strm_patchdist_fwd", _p(E), _p(plan.order), _p(dist), _p(idx), _p(logits), Ns, Nq, plan.way, shot, L, E.shape[1], _stream())
+    return logits, dist, idx
+
+
+def strm_patchdist_bwd(E, plan, dist, idx, g, Ns, Nq, L):
+    """g [Nq, way], explicit selections idx -> (dpre [NV*T, Hd] gradient before the ReLU, dP [NV*L, 2 Hd])"""
+    shot = _strm_plan_check(plan, Ns)
+    _strm_chk(E, dist, idx, g)
+    Hd = E.shape[1]
+    dpre = torch.empty_like(E)
+    dP = _empty(((Ns + Nq) * L, 2 * Hd), E)
+    lib().call("lmkd_strm_patchdist_bwd", _p(E), _p(plan.order), _p(plan.rowmap), _p(dist), _p(idx), _p(g), _p(dpre), _p(dP), Ns, Nq, plan.way,
+               shot, L, Hd, _stream())
+    return dpre, dP
+
+
+class PatchDistFn(torch.autograd.Function):
+    """DistanceLoss.forward (strm_res18_sup.py:188-243): dropout, clsW over frame pairs as two per-frame half projections, ReLU, per class
+    the minimum Euclidean distance over the class's support pair rows, mean over the pairs, negated -> [Nq, way]"""
+
+    @staticmethod
+    def forward(ctx, sup, qry, w, b, mask, plan):
+        Ns, L, Din = sup.shape
+        Nq = qry.shape[0]
+        X = stack_rows(sup.reshape(Ns * L, Din), qry.reshape(Nq * L, Din))
+        w = w.contiguous()
+        _strm_chk(X, w, b, mask)
+        if mask is not None:
+            Xd = torch.empty_like(X)
+            lib().call("lmkd_mul", _p(X), _p(mask), _p(Xd), X.numel(), _stream())
+        else:
+            Xd = X
+        P, E = strm_patchdist_embed(Xd, w, b, L)
+        logits, dist, idx = strm_patchdist_fwd(E, plan, Ns, Nq, L)
+        if STRM_TAPS is not None:
+            STRM_TAPS.setdefault("dist", []).append(idx)
+        ctx.save_for_backward(Xd, w, E, dist, idx, mask)
+        ctx.plan, ctx.dims = plan, (Ns, Nq, L)
+        return logits
+
+    @staticmethod
+    def backward(ctx, g):
+        _audit.engine_owned(g)
+        Xd, w, E, dist, idx, mask = ctx.saved_tensors
+        Ns, Nq, L = ctx.dims
+        dX, dw, db = strm_patchdist_grads(Xd, w, E, ctx.plan, dist, idx, g.contiguous(), mask, Ns, Nq, L)
+        Din = Xd.shape[1]
+        return dX[:Ns * L].view(Ns, L, Din), dX[Ns * L:].view(Nq, L, Din), dw, db, None, None
+
+
+def strm_patchdist_grads(Xd, w, E, plan, dist, idx, g, mask, Ns, Nq, L):
+    """the whole backward of PatchDistFn from explicit selections: Xd [NV*L, Din] (dropout applied), E = strm_patchdist_embed(Xd, ...)[1],
+    dist / idx [Nq*T, way] as strm_patchdist_fwd returns them, g [Nq, way] -> (dX [NV*L, Din], dclsW [Hd, 2 Din], dbias [Hd])"""
+    M, Din = Xd.shape
+    Hd = w.shape[0]
+    dpre, dP = strm_patchdist_bwd(E, plan, dist, idx, g, Ns, Nq, L)
+    db = colsum(dpre)
+    dw = _empty((Hd, 2 * Din), Xd)
+    gemm("M", "N", Hd, Din, M, dP, 2 * Hd, Xd, Din, dw, 2 * Din)                           # dclsW[:, :Din] = dP_a^T @ X
+    gemm("M", "N", Hd, Din, M, dP, 2 * Hd, Xd, Din, dw, 2 * Din, A_off=Hd, C_off=Din)      # dclsW[:, Din:] = dP_b^T @ X
+    dX = _empty((M, Din), Xd)
+    gemm("K", "N", M, Din, Hd, dP, 2 * Hd, w, 2 * Din, dX, Din)
+    gemm("K", "N", M, Din, Hd, dP, 2 * Hd, w, 2 * Din, dX, Din, beta=1.0, A_off=Hd, B_off=Din)
+    if mask is not None:
+        lib().call("lmkd_mul", _p(dX), _p(mask), _p(dX), dX.numel(), _stream())
+    return dX, dw, db

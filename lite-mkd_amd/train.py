@@ -6,8 +6,9 @@ train_wandb.sh):
         --checkpoint_dir hmdb_checkpoint/ --training_iterations 70010 --temp_set 2 --trans_linear_in_dim 2048
 
 Every flag of the reference's parser is accepted under its own name and default (so train_wandb.sh's command line parses unchanged);
-the defaults of the three plugin names are train_wandb.sh's values instead of the parser's (`strm18_student` / `TRX` / `test_teacher`
-are outside this build's scope).  What the reference does around the loop and this build does not: wandb logging (a
+the defaults of the three plugin names are train_wandb.sh's values instead of the parser's (`strm18_student` / `TRX` / `test_teacher`:
+the STRM student is available under its own names, `--model_backbone strm18_student --model_classifier strm_res18_sup --distill_name
+strm_fc_2_sup_dist`).  What the reference does around the loop and this build does not: wandb logging (a
 JSON-lines log instead, --log_jsonl).  Episodes come from SyntheticEpisodes, from the reference's own JPEG frame tree (--rgb_path,
 --traintestlist, --teacher_path: JpegFrameEpisodes, decoded on the GPU) or, with --data_dir, from a directory of decoded uint8 clips;
 the frame transform runs on the GPU.  One process per GPU: under torchrun every rank runs this script on its own episode stream

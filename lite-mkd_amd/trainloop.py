@@ -195,6 +195,21 @@ def end_episode(task_dict, train=True):
         tag[0].release(tag[1])
 
 
+# trainwandb.py:259-273 (training) and :305-337 (test): the logits the accuracy of the three STRM distillers is taken on
+STRM_ACCURACY = {"strm_fc_2_sup_dist": (0.2, ("fr1", "fr2")), "strm": (0.1, ("fr",)), "strm_KD": (0.1, ("fr",))}
+
+
+def strm_accuracy_logits(distill_name, logits):
+    """-> 0.2 * pat + fr1 + fr2 (strm_fc_2_sup_dist) / 0.1 * pat + fr (strm, strm_KD) on the device, or None for any other distiller"""
+    rule = STRM_ACCURACY.get(distill_name)
+    if rule is None or not isinstance(logits, dict) or "pat" not in logits:
+        return None
+    out = rule[0] * logits["pat"]
+    for k in rule[1]:
+        out = out + logits[k]
+    return out
+
+
 def _episode_forward(prepared, student, teacher, distiller, accuracy_fn, config):
     """forward + loss + accuracy of one episode (trainwandb.py:190-283) -> (task_loss with its autograd graph, accuracy)"""
     (context_images, target_images, context_teacher_feature, target_teacher_feature, context_labels,
@@ -214,7 +229,10 @@ def _episode_forward(prepared, student, teacher, distiller, accuracy_fn, config)
     task_loss = loss["loss"]
     if config.distill_name == "KL_feature":         # :243-244
         target_logits = target_logits["logits"]
-    if isinstance(target_logits, dict) and "kl" in target_logits and "ce" in target_logits:
+    strm_logits = strm_accuracy_logits(config.distill_name, target_logits)
+    if strm_logits is not None:
+        task_accuracy = accuracy_fn(strm_logits.detach(), target_labels)     # :259-273
+    elif isinstance(target_logits, dict) and "kl" in target_logits and "ce" in target_logits:
         task_accuracy, _ = ops.accuracy(target_logits["kl"], target_logits["ce"], target_labels)     # :247-257,278
     elif isinstance(target_logits, dict):
         task_accuracy = accuracy_fn(target_logits["kl"], target_labels)
@@ -933,7 +951,10 @@ def test_task(task_dict, model, accuracy_fn, config):
     """trainwandb.py:289-357 (student branch)."""
     (context_images, target_images, _, _, context_labels, target_labels, _, _) = prepare_task(task_dict, config.device)
     logits = model(context_images, context_labels, target_images)["logits"]
-    if isinstance(logits, dict) and "kl" in logits and "ce" in logits:
+    strm_logits = strm_accuracy_logits(getattr(config, "distill_name", None), logits)
+    if strm_logits is not None:
+        acc = accuracy_fn(strm_logits, target_labels)     # :305-337
+    elif isinstance(logits, dict) and "kl" in logits and "ce" in logits:
         acc, _ = ops.accuracy(logits["kl"], logits["ce"], target_labels)
     elif isinstance(logits, dict):
         acc = accuracy_fn(logits["kl"], target_labels)
