@@ -201,12 +201,8 @@ def _grad_target(param):
         return None
     # kernels of the side stream (query-frame trunk call: BatchNorm parameters) and of the auxiliary stream (second TRX head: TRX
     # parameters) add to the shadow buffer, everything on the caller's stream to .grad: no address is ever added to from two streams
-    cur = _raw_stream(param.device.index)
-    for table in (_side_streams, _aux_streams):
-        for key, other in table.items():
-            if key[1] == param.device.index and cur == other.cuda_stream:
-                return e[1]
-    return param.grad
+    dev = param.device.index
+    return e[1] if stream_role(_raw_stream(dev)) in ((dev, "side"), (dev, "aux")) else param.grad
 
 
 # Inference Linear on the bf16-plane convolution kernels: y = relu?(x W^T + b) is a 1x1 convolution over M one-pixel "frames" whose
@@ -933,17 +929,16 @@ SIDE_WGRAD = False
 # False: no wait at the end of backward(); the caller promises to call wait_weight_grads() before it reads or modifies any
 # weight.grad (trainloop.FusedOptimizer does, so the next episode's forward can overlap the last weight gradients)
 SYNC_WGRAD_AT_BACKWARD_END = True
-_WG_STREAM = {}
 _WG_CB = [None]      # id of the autograd graph task whose end-of-backward callback is queued (a backward that raised leaves a
                      # stale id behind, which the next backward — a new graph task — does not match)
 
 
 def wait_weight_grads():
     """make the current (and the default) stream wait for every weight gradient launched on the side stream"""
-    for dev, sw in _WG_STREAM.items():
-        torch.cuda.current_stream(dev).wait_stream(sw)
+    for sw in forked_streams(roles=("wgrad",)):
+        torch.cuda.current_stream(sw.device).wait_stream(sw)
         if not torch.cuda.is_current_stream_capturing():      # a wait on a capturing stream's event would pull the default stream into the capture
-            torch.cuda.default_stream(dev).wait_stream(sw)
+            torch.cuda.default_stream(sw.device).wait_stream(sw)
 
 
 def join_all_streams():
@@ -952,15 +947,14 @@ def join_all_streams():
     shadow): kernels on the side and auxiliary streams add parameter gradients directly (DIRECT_PARAM_GRAD), hand autograd None, and are
     therefore NOT joined to the caller's stream by the autograd engine; that the stem's weight gradient happens to order the side stream
     before the weight-gradient stream is not something to rely on (a frozen or hooked stem weight breaks it)."""
-    if not (_WG_STREAM or _side_streams or _aux_streams or _lane_mains):
+    if not _STREAMS:
         return      # nothing was ever forked (this includes every CPU-side caller)
     cur = torch.cuda.current_stream()
     dev = cur.device.index if hasattr(cur, "device") and cur.device is not None else torch.cuda.current_device()
     wait_weight_grads()
-    for table in (_side_streams, _aux_streams, _lane_mains):
-        for key, s in table.items():
-            if key[1] == dev and s.cuda_stream != cur.cuda_stream:
-                cur.wait_stream(s)
+    for s in forked_streams(torch.device("cuda", dev), roles=("side", "aux", "main")):
+        if s.cuda_stream != cur.cuda_stream:
+            cur.wait_stream(s)
 
 
 def _end_of_backward():
@@ -972,11 +966,16 @@ def _has_hooks(w):
     return bool(getattr(w, "_backward_hooks", None)) or bool(getattr(w, "_post_accumulate_grad_hooks", None))
 
 
-def _wgrad_stream(device):
-    dev = device_index(device)
-    if dev not in _WG_STREAM:
-        _WG_STREAM[dev] = _new_stream(device, "wgrad")
-    return _WG_STREAM[dev]
+def _on_wgrad_stream(device, work, reads):
+    """work() on the weight-gradient stream, after everything queued so far on the current stream; reads: the tensors (or None) it reads"""
+    sw = _wgrad_stream(device)
+    sw.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(sw):
+        work()
+    for t in reads:
+        if t is not None:
+            t.record_stream(sw)
+    _join_at_backward_end()
 
 
 def _join_at_backward_end():
@@ -1001,13 +1000,7 @@ def side_accumulate(param, fn, *reads):
     e = _GRAD_SLOT.get(param.data_ptr())
     if e is None or e[0]() is not param or param.grad is None:
         return False
-    sw = _wgrad_stream(param.device)
-    sw.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(sw):
-        fn(param.grad)
-    for t in reads:
-        t.record_stream(sw)
-    _join_at_backward_end()
+    _on_wgrad_stream(param.device, lambda: fn(param.grad), reads)
     return True
 
 
@@ -1015,9 +1008,8 @@ def weight_grad(w, x, dy, stride, pad, pre_stats=None, seg=0):
     """dW of a convolution for autograd — or None after accumulating it into w.grad on the weight-gradient stream."""
     if not (SIDE_WGRAD and w.is_leaf and w.requires_grad) or _has_hooks(w):
         return conv_bwd_weight(x, dy, tuple(w.shape), stride, pad, pre_stats, seg=seg)
-    sw = _wgrad_stream(x.device)
-    sw.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(sw):
+
+    def work():
         if w.grad is not None and w.grad.is_contiguous() and w.grad.dtype == torch.float32:
             conv_bwd_weight(x, dy, tuple(w.shape), stride, pad, pre_stats, acc_into=w.grad, seg=seg)      # += in the slab reduce
         else:
@@ -1026,16 +1018,10 @@ def weight_grad(w, x, dy, stride, pad, pre_stats=None, seg=0):
                 w.grad = dw
             else:
                 w.grad.add_(dw)
-    x.record_stream(sw)
-    dy.record_stream(sw)
-    for t in (x, dy):      # ... and the words holding their maxima (fp32h2): the side-stream kernel reads them when it starts
-        for attr in ("_lmkd_amax", "_lmkd_pre_amax"):
-            wm = getattr(t, attr, None)
-            if wm is not None:
-                wm.record_stream(sw)
-    if pre_stats is not None:      # read by the side-stream kernel too: its block must not be recycled under it
-        pre_stats.record_stream(sw)
-    _join_at_backward_end()
+    # read by the side-stream kernel: x, dy, the words holding their maxima (fp32h2: it reads them when it starts) and pre_stats - no
+    # block of theirs may be recycled under it
+    words = [getattr(t, attr, None) for t in (x, dy) for attr in ("_lmkd_amax", "_lmkd_pre_amax")]
+    _on_wgrad_stream(x.device, work, [x, dy] + words + [pre_stats])
     return None
 
 
@@ -1173,11 +1159,15 @@ def apply_deferred(entries, counters=None):
 # the forward of episode i + 1 beside the backward of episode i: the two episodes in flight use different lanes (LANE 0 / 1), each
 # with a main stream of its own (lane_main) in place of the caller's.
 LANE = [0]
-_side_streams = {}
-_lane_mains = {}
+# Every stream this module forks, in order of creation: (device index, lane, "main" | "side" | "aux") -> stream, and the device's
+# weight-gradient stream under (device index, None, "wgrad").  Nothing outside this section reads a key: the four getters
+# below create on first request (under the current lane), lane_streams / forked_streams / stream_role only look.
+_STREAMS = {}
+_STREAM_ROLE = {}      # raw handle -> (device index, role)
 # HIP stream priorities (torch: -1 = high, 0 = default) of the streams this module creates, by lane and for the weight-gradient stream;
 # set before the first stream is created (bench.py LMKD_PRIO)
 STREAM_PRIORITY = {0: 0, 1: 0, "wgrad": 0}
+HEADS_ON_TWO_STREAMS = True      # TRX_2fcsup: the 'ce' head on the auxiliary stream beside the 'kl' head
 
 
 def _new_stream(device, key):
@@ -1185,43 +1175,63 @@ def _new_stream(device, key):
 
 
 def device_index(device):
-    """the index the stream tables are keyed with: torch.device('cuda') (index None - the training CLI's default before init_distributed
+    """the index the stream table is keyed with: torch.device('cuda') (index None - the training CLI's default before init_distributed
     fills it in) means the current device"""
     device = torch.device(device)
     return device.index if device.index is not None else torch.cuda.current_device()
 
 
-def set_lane(k):
-    LANE[0] = int(k)
+@contextlib.contextmanager
+def lane(k):
+    """run the body under stream set k; the previous lane is restored afterwards, also when the body raises"""
+    prev, LANE[0] = LANE[0], int(k)
+    try:
+        yield
+    finally:
+        LANE[0] = prev
 
 
-def side_stream(device):
-    device = torch.device(device)
-    key = (device.type, device_index(device), LANE[0])
-    if key not in _side_streams:
-        _side_streams[key] = _new_stream(device, LANE[0])
-    return _side_streams[key]
+def _forked(device, lane, role):
+    """the one creating getter; lane None: the device's weight-gradient stream (role "wgrad", its STREAM_PRIORITY key)"""
+    dev = device_index(device)
+    if (dev, lane, role) not in _STREAMS:
+        s = _STREAMS[(dev, lane, role)] = _new_stream(device, role if lane is None else lane)
+        _STREAM_ROLE[s.cuda_stream] = (dev, role)
+    return _STREAMS[(dev, lane, role)]
 
 
 def lane_main(device):
-    device = torch.device(device)
-    key = (device.type, device_index(device), LANE[0])
-    if key not in _lane_mains:
-        _lane_mains[key] = _new_stream(device, LANE[0])
-    return _lane_mains[key]
+    return _forked(device, LANE[0], "main")
 
 
-HEADS_ON_TWO_STREAMS = True      # TRX_2fcsup: the 'ce' head on the auxiliary stream beside the 'kl' head
-_aux_streams = {}
+def side_stream(device):
+    return _forked(device, LANE[0], "side")
 
 
 def aux_stream(device):
     """a third forward stream: the frozen teacher head of an episode runs there beside the student's trunk (trainloop.train_task)"""
-    device = torch.device(device)
-    key = (device.type, device_index(device), LANE[0])
-    if key not in _aux_streams:
-        _aux_streams[key] = _new_stream(device, LANE[0])
-    return _aux_streams[key]
+    return _forked(device, LANE[0], "aux")
+
+
+def _wgrad_stream(device):
+    return _forked(device, None, "wgrad")
+
+
+def lane_streams(device, roles=("side", "aux", "main")):
+    """the streams of these roles that exist for the CURRENT lane on `device`, in the order of `roles`"""
+    keys = [(device_index(device), LANE[0], role) for role in roles]
+    return [_STREAMS[key] for key in keys if key in _STREAMS]
+
+
+def forked_streams(device=None, roles=("wgrad", "side", "aux", "main")):
+    """every stream of these roles created so far (on `device`; None: on any), role by role in the order of `roles`"""
+    dev = None if device is None else device_index(device)
+    return [s for role in roles for (d, _, r), s in _STREAMS.items() if r == role and (dev is None or d == dev)]
+
+
+def stream_role(raw):
+    """-> (device index, role) of the forked stream with this raw handle, None for any other stream"""
+    return _STREAM_ROLE.get(raw)
 
 
 FUSE_EVAL_BN = True      # eval mode: BatchNorm (+ residual, ReLU) in the convolution epilogue (lmkd_conv2d_fwd_bn)

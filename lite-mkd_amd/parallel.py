@@ -193,9 +193,8 @@ class EarlyAllReduce:
             self.stream = torch.cuda.Stream(device=b.grad.device)
         cs = self.stream
         cs.wait_stream(torch.cuda.current_stream())          # the stream of the node that just ran (the trunk call's own)
-        for table in (ops._WG_STREAM, ops._side_streams, ops._aux_streams, ops._lane_mains):
-            for s in table.values():
-                cs.wait_stream(s)
+        for s in ops.forked_streams():
+            cs.wait_stream(s)
         cs.wait_stream(torch.cuda.default_stream(b.grad.device))
         with torch.cuda.stream(cs):
             tail = b.grad[self.split:]

@@ -242,7 +242,7 @@ def _episode_forward(prepared, student, teacher, distiller, accuracy_fn, config)
 
 
 class PipelinedEpisodes:
-    """Software pipelining ACROSS episodes: the forward of episode i + 1 is queued (on the other stream set, ops.set_lane) before the
+    """Software pipelining ACROSS episodes: the forward of episode i + 1 is queued (on the other stream set, ops.lane) before the
     backward of episode i, so the two run side by side on the GPU.  Within one episode the launch sequence has stretches the chip
     cannot fill - the matcher / loss section between the trunk's forward and backward (~2 ms of 126-workgroup GEMMs and
     wavefront-reduction kernels on an otherwise idle chip), the stem / pooling passes, every convolution launch's last partial round
@@ -277,8 +277,7 @@ class PipelinedEpisodes:
         caller = torch.cuda.current_stream(dev)
         lane = self.count % (self.depth + 1)
         self.count += 1
-        ops.set_lane(lane)
-        try:
+        with ops.lane(lane):
             main = ops.lane_main(dev)
             main.wait_stream(caller)                 # the optimizer's weight update / zeroed gradients, the caller's input tensors
             with torch.cuda.stream(main):
@@ -286,32 +285,24 @@ class PipelinedEpisodes:
                 loss, acc = _episode_forward(prepared, self.student, self.teacher, self.distiller, self.accuracy_fn, self.config)
             self.queue.append((loss, acc, lane, task_dict))
             return self._backward(self.queue.pop(0)) if len(self.queue) > self.depth else None
-        finally:
-            ops.set_lane(0)
 
     def _backward(self, item):
         loss, acc, lane, task_dict = item
         dev = self.config.device
-        ops.set_lane(lane)
-        try:
+        with ops.lane(lane):
             main = ops.lane_main(dev)
             with torch.cuda.stream(main):
                 if self.bwd_done is not None:
                     main.wait_event(self.bwd_done)       # gradients accumulate in episode order
                 loss.backward(retain_graph=False)
                 end_episode(task_dict)
-                # the lane's side / auxiliary streams wrote parameter gradients directly (autograd got None and joined nothing): the
-                # event that orders the NEXT backward's accumulations must cover them
-                d = torch.device(dev)
-                for table in (ops._side_streams, ops._aux_streams):
-                    s = table.get((d.type, ops.device_index(d), lane))
-                    if s is not None:
-                        main.wait_stream(s)
+                # the lane's side / auxiliary streams (those that exist) wrote parameter gradients directly (autograd got None and joined
+                # nothing): the event that orders the NEXT backward's accumulations must cover them
+                for s in ops.lane_streams(dev, roles=("side", "aux")):
+                    main.wait_stream(s)
                 ev = torch.cuda.Event()
                 ev.record(main)
                 self.bwd_done = ev
-        finally:
-            ops.set_lane(0)
         return loss.detach(), acc
 
     def join(self):
@@ -487,13 +478,12 @@ class StreamedEpisodes:
 
     def release(self, k):
         """the episode that read set k has been queued completely (end_episode): record where every stream that may still read the set
-        stands - the copy stream waits for these before it overwrites the set - and record those streams on the set's tensors"""
+        stands - the copy stream waits for these before it overwrites the set - and record those streams on the set's tensors.  Only
+        streams of the loader's own device are looked at: one process drives one device"""
         s = self.sets[k]
         # the streams of the lane the episode ran on (end_episode runs under that lane) and the weight-gradient stream - not every stream of
         # every lane (twice as many events to record and for the copy stream to wait for)
-        streams = [torch.cuda.current_stream(self.device)] + list(ops._WG_STREAM.values())
-        for table in (ops._side_streams, ops._aux_streams, ops._lane_mains):
-            streams += [st for key, st in table.items() if key[2] == ops.LANE[0]]
+        streams = [torch.cuda.current_stream(self.device)] + ops.forked_streams(self.device, roles=("wgrad",)) + ops.lane_streams(self.device)
         seen = set()
         for st in streams:
             if st.cuda_stream in seen:
@@ -664,33 +654,45 @@ class GraphedEpisode:
         from .model.classifiers.TRX_2fcsup import TemporalCrossTransformer as T
         return [T.draw_dropout_seed() for _ in range(n)]
 
-    def _capture(self, task_dict, key):
+    def _capture(self, task_dicts, sync_wgrad):
+        """one graph of these episodes in turn.  sync_wgrad (ops.SYNC_WGRAD_AT_BACKWARD_END during the capture): the weight-gradient stream
+        joins the capture stream at the end of every backward pass - or, False, runs on under the next episode's forward and joins once, at
+        the end.  -> (entry dict with the graph and its seed slots, prepared episodes, their class plans, [(loss, accuracy)])"""
         cfg = self.config
-        prepared = prepare_task(task_dict, cfg.device)
-        labels = prepared[4]
-        plan = ops.get_plan(labels, cfg.way)                       # built (H2D copies) outside the capture; the capture finds it cached
-        plan.full_rowmap(prepared[2].shape[0] + prepared[3].shape[0])
-        plan.full_rowmap(prepared[0].shape[0] // cfg.seq_len + prepared[1].shape[0] // cfg.seq_len)
-        streams = [ops.side_stream(cfg.device), ops.aux_stream(cfg.device)] + list(ops._WG_STREAM.values())
-        ops.refresh_packs(streams)
-        slots = ops.SeedSlots(cfg.device)
+        prepared = [prepare_task(t, cfg.device) for t in task_dicts]
+        plans = []
+        for pr in prepared:
+            plan = ops.get_plan(pr[4], cfg.way)                    # built (H2D copies) outside the capture; the capture finds it cached
+            plan.full_rowmap(pr[2].shape[0] + pr[3].shape[0])
+            plan.full_rowmap(pr[0].shape[0] // cfg.seq_len + pr[1].shape[0] // cfg.seq_len)
+            plans.append(plan)
+        ops.refresh_packs([ops.side_stream(cfg.device), ops.aux_stream(cfg.device)] + ops.forked_streams(roles=("wgrad",)))
+        slots = ops.SeedSlots(cfg.device, n=16 * len(prepared))
         g = torch.cuda.CUDAGraph()
         prev_sync = ops.SYNC_WGRAD_AT_BACKWARD_END
         torch.cuda.synchronize()
         ops.SEED_SLOTS = slots
-        ops.SYNC_WGRAD_AT_BACKWARD_END = True                      # every forked stream joins the capture stream before it ends
+        ops.SYNC_WGRAD_AT_BACKWARD_END = sync_wgrad
         ops.amax_pool_reset()                                      # fp32h2: the words of the tensors' maxima come from a pool zeroed inside THIS graph
+        out = []
         try:
             with torch.cuda.graph(g):
-                loss, acc, _ = _train_task_prepared(prepared, self.student, self.teacher, self.distiller, self.accuracy_fn, cfg)
-                ops.wait_weight_grads()
+                for pr, plan in zip(prepared, plans):
+                    ops._plan_cache[0], ops._plan_cache[1], ops._plan_cache[2] = pr[4], cfg.way, plan      # (get_plan's one-entry identity cache)
+                    loss, acc, _ = _train_task_prepared(pr, self.student, self.teacher, self.distiller, self.accuracy_fn, cfg)
+                    out.append((loss, acc))
+                ops.wait_weight_grads()                            # every forked stream joins the capture stream before it ends
         finally:
             ops.SEED_SLOTS = None
             ops.SYNC_WGRAD_AT_BACKWARD_END = prev_sync
+        return {"graph": g, "slots": slots}, prepared, plans, out
+
+    def _capture_episode(self, task_dict, key):
+        ent, (prepared,), (plan,), ((loss, acc),) = self._capture([task_dict], True)
         # the entry HOLDS the episode's tensors (their addresses cannot be recycled while it lives) and remembers their in-place
         # versions: a replay is only valid for these very tensors with unchanged contents (_resident)
-        ent = {"graph": g, "slots": slots, "loss": loss, "acc": acc, "prepared": prepared, "plan": plan, "counts": tuple(plan.counts),
-               "task": task_dict, "versions": tuple(task_dict[k]._version for k in self.KEYS)}
+        ent.update(loss=loss, acc=acc, prepared=prepared, plan=plan, counts=tuple(plan.counts), task=task_dict,
+                   versions=tuple(task_dict[k]._version for k in self.KEYS))
         self.graphs[key] = ent
         return ent
 
@@ -705,12 +707,15 @@ class GraphedEpisode:
         return (all(task_dict[k] is ent["task"][k] for k in self.KEYS)
                 and tuple(task_dict[k]._version for k in self.KEYS) == ent["versions"])
 
-    def _replay(self, ent, task_dict):
+    def _launch(self, ent, episodes):
         ops.wait_weight_grads()                                        # an eager episode's weight gradients may still be in flight
         ops.refresh_packs()
         ent["slots"].stage(self._seeds(ent["slots"].used))
         ent["graph"].replay()
-        self.replays += 1
+        self.replays += episodes
+
+    def _replay(self, ent, task_dict):
+        self._launch(ent, 1)
         loss, acc = ent["loss"].clone(), ent["acc"].clone()            # the graph's output tensors are overwritten by the next replay
         end_episode(task_dict)                                         # (the eager paths end theirs in train_task)
         return loss, acc, {"accuracy": acc}
@@ -729,7 +734,7 @@ class GraphedEpisode:
                 self.seen.add(("generic",) + shapes)
                 return self._eager(task_dict)
             static = {k: v.detach().to(cfg.device).clone() if k in self.KEYS else v for k, v in task_dict.items()}
-            ent = self._capture(static, ("generic",) + shapes)
+            ent = self._capture_episode(static, ("generic",) + shapes)
             return self._replay(ent, task_dict)
         if tuple(plan.counts) != ent["counts"] or plan.classes != ent["plan"].classes:
             return self._eager(task_dict)
@@ -756,47 +761,13 @@ class GraphedEpisode:
             if ikey not in self.seen:
                 self.seen.add(ikey)
                 return [self._eager(t) for t in task_dicts]
-            ent = self._capture_interval(task_dicts, ikey)
-        ops.wait_weight_grads()
-        ops.refresh_packs()
-        ent["slots"].stage(self._seeds(ent["slots"].used))
-        ent["graph"].replay()
-        self.replays += len(task_dicts)
+            ent, prepared, plans, out = self._capture(task_dicts, False)
+            ent.update(out=out, prepared=prepared, plans=plans, tasks=list(task_dicts))
+            self.graphs[ikey] = ent
+        # no end_episode here, unlike _replay: resident episodes hold no input set and a capture leaves the range fence nothing to judge
+        self._launch(ent, len(task_dicts))
         out = [(l.clone(), a.clone()) for l, a in ent["out"]]
         return [(l, a, {"accuracy": a}) for l, a in out]
-
-    def _capture_interval(self, task_dicts, ikey):
-        cfg = self.config
-        prepared = [prepare_task(t, cfg.device) for t in task_dicts]
-        plans = []
-        for pr in prepared:
-            plan = ops.get_plan(pr[4], cfg.way)
-            plan.full_rowmap(pr[2].shape[0] + pr[3].shape[0])
-            plan.full_rowmap(pr[0].shape[0] // cfg.seq_len + pr[1].shape[0] // cfg.seq_len)
-            plans.append(plan)
-        streams = [ops.side_stream(cfg.device), ops.aux_stream(cfg.device)] + list(ops._WG_STREAM.values())
-        ops.refresh_packs(streams)
-        slots = ops.SeedSlots(cfg.device, n=16 * len(prepared))
-        g = torch.cuda.CUDAGraph()
-        prev_sync = ops.SYNC_WGRAD_AT_BACKWARD_END
-        torch.cuda.synchronize()
-        ops.SEED_SLOTS = slots
-        ops.SYNC_WGRAD_AT_BACKWARD_END = False                     # the weight-gradient stream runs on under the next episode's forward ...
-        ops.amax_pool_reset()
-        out = []
-        try:
-            with torch.cuda.graph(g):
-                for pr, plan in zip(prepared, plans):
-                    ops._plan_cache[0], ops._plan_cache[1], ops._plan_cache[2] = pr[4], cfg.way, plan      # (get_plan's one-entry identity cache)
-                    loss, acc, _ = _train_task_prepared(pr, self.student, self.teacher, self.distiller, self.accuracy_fn, cfg)
-                    out.append((loss, acc))
-                ops.wait_weight_grads()                            # ... and joins the capture stream once, at the end
-        finally:
-            ops.SEED_SLOTS = None
-            ops.SYNC_WGRAD_AT_BACKWARD_END = prev_sync
-        ent = {"graph": g, "slots": slots, "out": out, "prepared": prepared, "plans": plans, "tasks": list(task_dicts)}
-        self.graphs[ikey] = ent
-        return ent
 
     def __call__(self, task_dict):
         key = self._key(task_dict)
@@ -811,7 +782,7 @@ class GraphedEpisode:
                 return self._eager(task_dict)
             if sum(1 for k in self.graphs if k[0] != "generic") >= self.max_graphs:
                 return self._generic(task_dict)
-            ent = self._capture(task_dict, key)
+            ent = self._capture_episode(task_dict, key)
         elif not self._resident(ent, task_dict):
             # same addresses, other tensors or modified contents: not the resident episode this graph was captured on
             del self.graphs[key]

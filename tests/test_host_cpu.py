@@ -392,3 +392,69 @@ def test_conv_plan_reports_match_golden():
                 if a != b:
                     bad.append("%s | %s | %s: %d, golden %d" % (st, sk, f, a, b))
     assert not bad, "%d differences:\n%s" % (len(bad), "\n".join(bad[:40]))
+
+
+def test_stream_registry_on_stand_in_streams(monkeypatch):
+    """the one table of forked streams (ops: lane_main / side_stream / aux_stream / _wgrad_stream, lane_streams, forked_streams,
+    stream_role, lane) with stand-in stream objects: no GPU involved"""
+    from litemkd_amd import ops
+    made = []
+
+    def factory(device, key):
+        made.append(types.SimpleNamespace(cuda_stream=1000 + len(made), device=device, priority_key=key))
+        return made[-1]
+    monkeypatch.setattr(ops, "_new_stream", factory)
+    monkeypatch.setattr(ops, "_STREAMS", {})
+    monkeypatch.setattr(ops, "_STREAM_ROLE", {})
+    monkeypatch.setattr(ops, "LANE", [0])
+    d0, d1 = torch.device("cuda", 0), torch.device("cuda", 1)
+    getters = {"main": ops.lane_main, "side": ops.side_stream, "aux": ops.aux_stream}
+
+    # queries on an empty table find nothing and create nothing
+    assert ops.lane_streams(d0) == [] and ops.forked_streams() == [] and ops.forked_streams(d0) == [] and ops.stream_role(1000) is None
+    assert made == []
+
+    # a getter creates once per (device, lane, role), under the current lane, with the lane (or "wgrad") as its priority key
+    by = {}
+    for k in (0, 1, 2):
+        with ops.lane(k):
+            for role, get in getters.items():
+                by[k, role] = get(d0)
+                assert get(d0) is by[k, role] and by[k, role].priority_key == k
+    wg = ops._wgrad_stream(d0)
+    with ops.lane(2):
+        assert ops._wgrad_stream(d0) is wg and wg.priority_key == "wgrad"      # one per device, whatever the lane
+    other = ops.side_stream(d1)
+    assert len(made) == 11 and len({id(s) for s in made}) == 11
+    assert ops.side_stream(d0) is by[0, "side"] and ops.LANE[0] == 0
+
+    # the queries return exactly what was created, in the order asked for, and create nothing
+    for k in (0, 1, 2):
+        with ops.lane(k):
+            assert ops.lane_streams(d0) == [by[k, "side"], by[k, "aux"], by[k, "main"]]
+            assert ops.lane_streams(d0, roles=("side", "aux")) == [by[k, "side"], by[k, "aux"]]
+    with ops.lane(1):
+        assert ops.lane_streams(d1) == []
+    with ops.lane(5):
+        assert ops.lane_streams(d0) == []                                      # a lane without streams
+    assert ops.lane_streams(d1) == [other]
+    assert ops.forked_streams(d0, roles=("wgrad",)) == [wg] and ops.forked_streams(d1, roles=("wgrad",)) == []
+    assert ops.forked_streams(d0, roles=("side", "aux", "main")) == [by[k, r] for r in ("side", "aux", "main") for k in (0, 1, 2)]
+    assert ops.forked_streams(d0) == [wg] + ops.forked_streams(d0, roles=("side", "aux", "main"))
+    assert sorted(s.cuda_stream for s in ops.forked_streams()) == sorted(s.cuda_stream for s in made)
+    assert len(made) == 11
+
+    # the reverse lookup tells the side / auxiliary streams of every lane from main, weight-gradient and foreign streams
+    for (k, role), s in by.items():
+        assert ops.stream_role(s.cuda_stream) == (0, role)
+    assert ops.stream_role(wg.cuda_stream) == (0, "wgrad") and ops.stream_role(other.cuda_stream) == (1, "side")
+    assert ops.stream_role(0) is None and ops.stream_role(999) is None
+
+    # lane() restores the previous lane, also when the body raises, also nested
+    with ops.lane(1):
+        with pytest.raises(KeyError):
+            with ops.lane(2):
+                assert ops.LANE[0] == 2
+                raise KeyError("boom")
+        assert ops.LANE[0] == 1
+    assert ops.LANE[0] == 0
