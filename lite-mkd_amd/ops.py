@@ -1782,7 +1782,7 @@ def jpeg_decode_host(blobs):
 GRAD_READY_HOOK = None
 
 
-# Test aid: with BLOCK_TAPS set to a list, every BasicBlockFn / StemFn training forward appends its BatchNorm inputs and
+# Test aid: with BLOCK_TAPS set to a list, every BasicBlockFn / BottleneckFn / StemFn training forward appends its BatchNorm inputs and
 # statistics, so a test can reproduce the exact ReLU masks the HIP backward uses (mask flips at pre-activations within fp32
 # rounding of zero are the one legitimate source of percent-level gradient differences between two fp32 implementations).
 BLOCK_TAPS = None
@@ -1801,7 +1801,7 @@ def split_block_taps(taps):
             for key, v in t.items():
                 if key == "seg":
                     continue
-                d[key] = v[k] if key in ("stem_st", "st1") else (v[:s] if k == 0 else v[s:])
+                d[key] = v[k] if key in ("stem_st", "st1", "st2") else (v[:s] if k == 0 else v[s:])
             calls[k].append(d)
     return calls[0] + calls[1]
 
@@ -1941,6 +1941,8 @@ class BottleneckFn(torch.autograd.Function):
         ctx.training, ctx.stride, ctx.has_ds, ctx.fused = training, stride, wd is not None, fused
         ctx.seg = seg
         ctx.betas = (b1, b2, b3, bd)
+        if BLOCK_TAPS is not None and training:      # c1 / c2: the raw convolution outputs in both forms (pre and materialised)
+            BLOCK_TAPS.append({"c1": c1, "st1": st1, "c2": c2, "st2": st2, "y": y, "seg": seg})
         if training:
             ctx.save_for_backward(x, w1, g1, c1, st1, a1, w2, g2, c2, st2, a2, w3, g3, c3, st3, ybits if fused else y, wd, gd, cd, std)
             ctx.amax = tuple(_amax_tag(t) for t in (x, a1, a2, c1, c2))

@@ -96,7 +96,7 @@ def _bn(x, sd, prefix, training, update_running=True):
 
 
 # Test hook: when set, every ReLU of the trunks calls RELU_HOOK(pre_activation) instead of F.relu, in execution order (stem,
-# then relu1 / relu2 of each block; support call first, then query call).  The parity tests use it to impose the ReLU masks of
+# then relu1 / relu2 of each BasicBlock, relu1 / relu2 / relu3 of each Bottleneck; support call first, then query call).  The parity tests use it to impose the ReLU masks of
 # the implementation under test on the fp32 and fp64 oracle runs: two fp32 evaluations of a ReLU network legitimately differ
 # where a pre-activation lies within rounding of zero, and with the masks fixed the backward is a linear map that must agree to
 # fp32 rounding.
@@ -257,19 +257,19 @@ def init_trunk_from_shapes(shapes, gen):
 
 def resnet50_trunk(x, sd, training=True, update_running=True):
     x = F.conv2d(x, sd["0.weight"], None, 2, 3)
-    x = F.relu(_bn(x, sd, "1", training, update_running))
-    x = F.max_pool2d(x, 3, 2, 1)
+    x = _relu(_bn(x, sd, "1", training, update_running))
+    x = _maxpool_stem(x)
     for idx, width, n, stride in RESNET50_STAGES:
         for b in range(n):
             p = "%d.%d" % (idx, b)
             s = stride if b == 0 else 1
             idn = x
-            out = F.relu(_bn(F.conv2d(x, sd[p + ".conv1.weight"]), sd, p + ".bn1", training, update_running))
-            out = F.relu(_bn(F.conv2d(out, sd[p + ".conv2.weight"], None, s, 1), sd, p + ".bn2", training, update_running))
+            out = _relu(_bn(F.conv2d(x, sd[p + ".conv1.weight"]), sd, p + ".bn1", training, update_running))
+            out = _relu(_bn(F.conv2d(out, sd[p + ".conv2.weight"], None, s, 1), sd, p + ".bn2", training, update_running))
             out = _bn(F.conv2d(out, sd[p + ".conv3.weight"]), sd, p + ".bn3", training, update_running)
             if (p + ".downsample.0.weight") in sd:
                 idn = _bn(F.conv2d(x, sd[p + ".downsample.0.weight"], None, s, 0), sd, p + ".downsample.1", training, update_running)
-            x = F.relu(out + idn)
+            x = _relu(out + idn)
     return x
 
 

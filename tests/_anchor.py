@@ -39,6 +39,18 @@ def anchored_dict(hip, cpu32, ref64, factor=3.0, floor=2e-6, zero_scale=1e-7):
     return worst
 
 
+def near_zero_limit(t64, t32=None, rel=1e-5):
+    """how far from zero (from a tie) an fp64 pre-activation (a pooling candidate) may lie where the implementation under test resolved
+    its sign (its arg-max) the other way: rel x max |t64| - fp32 rounding of the value itself - or, where the fp32 reference's value of
+    the same tensor is given, 3 x that reference's own largest deviation from fp64 if that is more.  (Fifty layers deep the fp32
+    reference itself is 1e-4 max |t| away from fp64 and flips masks at 2.6e-5 max |t|: measured for oracle.resnet50_trunk at 64 and 96 px.
+    An evaluation with error e can flip a sign only where |t64| <= e; the factor 3 is the one of anchored().)"""
+    lim = rel * float(t64.abs().max())
+    if t32 is not None:
+        lim = max(lim, 3.0 * float((t32.double() - t64.double()).abs().max()))
+    return lim
+
+
 def record(name, pairs):
     """append the measured (HIP-vs-fp64, torch-CPU-fp32-vs-fp64) relative-L2 error pairs of an anchored test to the file named
     by $LMKD_PARITY_LOG (the GPU run that produces profiles/rNN_parity_errors.txt sets it), so the fp32-class claim of the

@@ -7,7 +7,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from _anchor import anchored, anchored_dict
+from _anchor import anchored, anchored_dict, near_zero_limit
 
 pytestmark = pytest.mark.gpu
 
@@ -95,8 +95,9 @@ class _MaskedReLU(torch.autograd.Function):
 
 
 def _hip_relu_masks(taps):
-    """ReLU masks of the HIP trunk calls in the oracle's ReLU order (stem, relu1, relu2 per block; support call, then query),
-    NCHW bool on the CPU.  relu1 = fmaf(c1, scale, shift) > 0, exactly what the kernels compute (lmkd_bn_apply)."""
+    """ReLU masks of the HIP trunk calls in the oracle's ReLU order (stem, relu1, relu2 per BasicBlock, relu1, relu2, relu3 per
+    Bottleneck; support call, then query), NCHW bool on the CPU.  relu1 = fmaf(c1, scale, shift) > 0 (Bottleneck: relu2 from c2 likewise),
+    exactly what the kernels compute (lmkd_bn_apply)."""
     from litemkd_amd import ops
     masks = []
     for t in taps:
@@ -104,6 +105,8 @@ def _hip_relu_masks(taps):
             masks.append((ops.bn_apply(t["stem_c"], t["stem_st"], True) > 0).permute(0, 3, 1, 2).cpu())
         else:
             masks.append((ops.bn_apply(t["c1"], t["st1"], True) > 0).permute(0, 3, 1, 2).cpu())
+            if "c2" in t:      # Bottleneck entry: three masks
+                masks.append((ops.bn_apply(t["c2"], t["st2"], True) > 0).permute(0, 3, 1, 2).cpu())
             masks.append((t["y"] > 0).permute(0, 3, 1, 2).cpu())
     return masks
 
@@ -157,7 +160,7 @@ def _episode_matches_oracle(dev, shot, query, img, clf, dist, bb, bf16=False, tr
     from litemkd_amd import ops
     from litemkd_amd.model.backbone import resnet as R
     from oracle import ref_cpu as O
-    impose = bb == "resnet18_2fc"          # BasicBlock trunks: the oracle runs with the HIP path's own ReLU masks imposed
+    impose = bb in ("resnet18_2fc", "resnet50_2fc")      # the oracle runs with the HIP path's own ReLU masks and pooling selections imposed
     args = default_args(shot=shot, query_per_class=query, img_size=img, trans_dropout=0.0, device=dev, model_classifier=clf,
                         model_backbone=bb)
     torch.manual_seed(1)
@@ -185,6 +188,8 @@ def _episode_matches_oracle(dev, shot, query, img, clf, dist, bb, bf16=False, tr
     pools = _hip_pool_choices(taps) if impose else None
     flips = [0, 0]
     pflips = [0, 0]
+    deep = bb == "resnet50_2fc"      # the fp32 oracle run (masks imposed) leaves its pre-activations / pooling inputs here for the fp64 run's limits
+    ref32 = {}
 
     def oracle(dt, imposed):
         p = {k: (v.clone().to(dt) if v.is_floating_point() else v.clone()) for k, v in sp.items()}
@@ -197,13 +202,16 @@ def _episode_matches_oracle(dev, shot, query, img, clf, dist, bb, bf16=False, tr
         def hook(t):
             m = masks[site[0]]
             site[0] += 1
+            if deep and dt == torch.float32:
+                ref32["relu", site[0]] = t.detach()
             if dt == torch.float64:        # a mask may differ from the fp64 one only where the pre-activation is within rounding of 0
                 diff = m != (t.detach() > 0)
                 flips[0] += int(diff.sum())
                 flips[1] += m.numel()
                 # bf16 mode: an activation within fp32 rounding of a bf16 rounding boundary rounds the other way in the other
                 # implementation (1 bf16 ulp = 0.4 %), so downstream pre-activations agree to ~1e-4, not 1e-6
-                lim = ((3e-2 if O.ACT_BF16 else 1e-2) if bf16 else 1e-5) * float(t.detach().abs().max())
+                # Bottleneck trunks (50 layers): or within 3 x the fp32 oracle's own deviation from fp64 at this site (_anchor.near_zero_limit)
+                lim = near_zero_limit(t.detach(), ref32.get(("relu", site[0])), (3e-2 if O.ACT_BF16 else 1e-2) if bf16 else 1e-5)
                 assert not bool(diff.any()) or float(t.detach()[diff].abs().max()) < lim, site[0]
             return _MaskedReLU.apply(t, m.to(dt))
         psite = {"stem": 0, "head": 0}
@@ -214,12 +222,14 @@ def _episode_matches_oracle(dev, shot, query, img, clf, dist, bb, bf16=False, tr
             idx = pools[psite[kind]][kind]
             psite[kind] += 1
             v = t.flatten(2).gather(2, idx.flatten(2)).reshape(idx.shape)
+            if deep and dt == torch.float32:
+                ref32[kind, psite[kind]] = t.detach()
             if dt == torch.float64:
                 nat = (F.max_pool2d(t.detach(), 3, 2, 1) if kind == "stem" else F.adaptive_max_pool2d(t.detach(), (4, 4)))
                 d = (nat - v.detach())
                 pflips[0] += int((d > 0).sum())
                 pflips[1] += d.numel()
-                lim = ((3e-2 if O.ACT_BF16 else 1e-2) if bf16 else 1e-5) * float(t.detach().abs().max())
+                lim = near_zero_limit(t.detach(), ref32.get((kind, psite[kind])), (3e-2 if O.ACT_BF16 else 1e-2) if bf16 else 1e-5)
                 assert float(d.max()) <= lim, (kind, float(d.max()), lim)
             return v
         O.RELU_HOOK = hook if imposed else None
@@ -273,7 +283,7 @@ def _episode_matches_oracle(dev, shot, query, img, clf, dist, bb, bf16=False, tr
     clear = (srt[:, -1] - srt[:, -2]) > (1.0 if bf16 else 5e-2)
     assert torch.equal(pred.cpu()[clear], torch.argmax(lg, -1)[clear])
     # gradients of every parameter, fp64-anchored (tests/_anchor.py): per tensor, the HIP gradient's relative-L2 error against
-    # the oracle run in fp64 is at most 3x the error of the oracle's own fp32 run.  For the BasicBlock trunks both oracle runs use
+    # the oracle run in fp64 is at most 3x the error of the oracle's own fp32 run.  Both oracle runs use
     # the HIP path's own ReLU masks (checked above to differ from fp64's only at pre-activations within rounding of zero): one
     # flipped mask moves a small-map channel gradient by 1e-3 of the tensor norm in EITHER fp32 evaluation, which a fixed budget
     # can only absorb by being loose enough to hide a scheduling bug.
@@ -299,7 +309,9 @@ def _episode_matches_oracle(dev, shot, query, img, clf, dist, bb, bf16=False, tr
             # fall differently; measured up to 7.6e-5 on layer-1 / stem BatchNorm parameters in the 64-px episodes, while the block
             # tests, where every mask is imposed, hold the 2e-6 floor at 200 frames in the same arithmetic)
             # (round 3, later: the pooling selections ARE imposed now for the BasicBlock trunks - _hip_pool_choices / oracle.POOL_HOOK -
-            # so what remains there is a linear map; the ResNet-50 cases, whose masks and selections are not imposed, keep 1e-4)
+            # so what remains there is a linear map; the ResNet-50 cases, whose masks and selections were not imposed then, kept 1e-4)
+            # (round 6: imposed for the Bottleneck trunks too - ops.BottleneckFn taps, oracle.resnet50_trunk through the hooks: the CPU pair
+            # of the 64-px ResNet-50 episodes drops from 4e-3 ... 7e-3 to the 1e-5 class, so factor 3 binds there as well)
             e_hip, e_cpu = anchored(k, pg[k].grad, sp32[k].grad, sp64[k].grad, factor, 1e-4, 1e-7 * gmax)
             worst = max(worst, (e_hip / (e_cpu + 1e-6), k, e_hip, e_cpu))
     print("worst HIP/CPU gradient error ratio vs fp64:", worst, "loss", loss.item(), ol.item(), ol64.item(), "mask flips vs fp64:", flips,

@@ -82,12 +82,29 @@ def _ulp_close(name, hip16, ref64):
     return frac
 
 
-def _run_shape(dev, name, H, Cs, Cin, Cout, K, s, p, N=FRAMES, check_wgrad=True, act16=False, trained=False):
-    """act16 (BASELINE configs[2]: ops.set_conv_compute_dtype('bf16') + set_activation_dtype('bf16') by the caller): x / dy / y / dx
+def _run_shape(dev, name, H, Cs, Cin, Cout, K, s, p, N=FRAMES, check_wgrad=True, act16=False, trained=False, seen=None, tiles=None):
+    """seen: the sets that collect which kernel instances ran (default: this module's SEEN, which the *_instances_were_exercised tests
+    read; a caller with shapes of its own passes its own dict).  tiles = (forward, data gradient): lmkd_conv_set_tile ids pinned for
+    those two launches (and their accumulate form), the weight gradient runs unpinned; the override is 0 again on return.
+    act16 (BASELINE configs[2]: ops.set_conv_compute_dtype('bf16') + set_activation_dtype('bf16') by the caller): x / dy / y / dx
     are bf16 tensors (the stem's NHWC4 input stays fp32), the kernels round the weights to one bf16 plane; the references are
     fp64 convolutions of the SAME bf16-rounded operands, so what is judged is the accumulation and the output rounding."""
+    import litemkd_amd
+    try:
+        return _run_shape_body(dev, name, H, Cs, Cin, Cout, K, s, p, N, check_wgrad, act16, trained, SEEN if seen is None else seen, tiles)
+    finally:
+        if tiles is not None:
+            litemkd_amd.lib().call("lmkd_conv_set_tile", 0)
+
+
+def _run_shape_body(dev, name, H, Cs, Cin, Cout, K, s, p, N, check_wgrad, act16, trained, seen, tiles):
+    import litemkd_amd
     from litemkd_amd import ops
     from _anchor import record
+
+    def pin(i):
+        if tiles is not None:
+            litemkd_amd.lib().call("lmkd_conv_set_tile", tiles[i] if i is not None else 0)
     g = torch.Generator(device=dev).manual_seed(zlib.crc32(name.encode()) % 10007)
     x = torch.randn(N, H, H, Cs, device=dev, generator=g)
     if Cs != Cin:
@@ -121,6 +138,7 @@ def _run_shape(dev, name, H, Cs, Cin, Cout, K, s, p, N=FRAMES, check_wgrad=True,
     w64 = (_r16(w) if act16 else w).cpu().double()
     res = {}
     # ---- forward (+ BatchNorm partial sums in the epilogue)
+    pin(0)
     y, part = ops.conv_fwd(xk, ops.pack_weights(w, Cs, 0), Cout, K, K, s, p, True)
     ref = F.conv2d(xs64, w64, None, s, p)
     if act16:
@@ -134,10 +152,11 @@ def _run_shape(dev, name, H, Cs, Cin, Cout, K, s, p, N=FRAMES, check_wgrad=True,
     # per-tile fp32 sums of the fp32 accumulators, combined in fp64: error relative to the sum of magnitudes
     assert torch.allclose(sums[:, 0], yd.sum(0), rtol=0, atol=2e-6 * float(yd.abs().sum(0).max())), name + " BN sum"
     assert torch.allclose(sums[:, 1], (yd * yd).sum(0), rtol=1e-5), name + " BN sum of squares"
-    SEEN["gemm"].add(plan(0, N, H, Cs, Cin, Cout, K, s, p)[:2])
-    SEEN["x3"].add(plan(0, N, H, Cs, Cin, Cout, K, s, p)[::4])      # (tile id, LDS-patch kernel?)
+    seen["gemm"].add(plan(0, N, H, Cs, Cin, Cout, K, s, p)[:2])
+    seen["x3"].add(plan(0, N, H, Cs, Cin, Cout, K, s, p)[::4])      # (tile id, LDS-patch kernel?)
     # ---- data gradient (+ the accumulate epilogue at full size)
     if Cin != 3:
+        pin(1)
         wd = ops.pack_weights(w, Cin, 1)
         dx = ops.conv_bwd_data(dyk, wd, (N, H, H, Cin), Cout, K, K, s, p)
         dys64 = nchw(dy[sub]).cpu().double()
@@ -158,9 +177,10 @@ def _run_shape(dev, name, H, Cs, Cin, Cout, K, s, p, N=FRAMES, check_wgrad=True,
             ops.conv_bwd_data(dy, wd, (N, H, H, Cin), Cout, K, K, s, p, out=acc, accumulate=True)
             # out += dgrad: one fp32 add per element on top of the plain result
             assert float((acc - (r + dx)).abs().max()) <= 1e-6 * float(dx.abs().max()) + 1e-6 * float(r.abs().max()), name + " dgrad accumulate"
-        SEEN["gemm"].add(plan(1, N, H, Cs, Cin, Cout, K, s, p)[:2])
+        seen["gemm"].add(plan(1, N, H, Cs, Cin, Cout, K, s, p)[:2])
     # ---- weight gradient over all frames (fp32 output in every mode; bf16 tensors: from the rounded x and dy)
     if check_wgrad:
+        pin(None)
         dw = ops.conv_bwd_weight(xk, dyk, (Cout, Cin, K, K), s, p)
         x64 = nchw(x[..., :Cin]).cpu().double()
         dy64 = nchw(dy).cpu().double()
@@ -169,8 +189,8 @@ def _run_shape(dev, name, H, Cs, Cin, Cout, K, s, p, N=FRAMES, check_wgrad=True,
         wr32 = w64.float().requires_grad_()
         F.conv2d(x64.float(), wr32, None, s, p).backward(dy64.float())
         res["wgrad"] = anchored(name + " wgrad", dw, wr32.grad, wr.grad)
-        SEEN["wgrad"].add(plan(2, N, H, Cs, Cin, Cout, K, s, p)[:2])
-        SEEN["x3w"].add(plan(2, N, H, Cs, Cin, Cout, K, s, p)[::4])      # (tile id, rolling-window kernel?)
+        seen["wgrad"].add(plan(2, N, H, Cs, Cin, Cout, K, s, p)[:2])
+        seen["x3w"].add(plan(2, N, H, Cs, Cin, Cout, K, s, p)[::4])      # (tile id, rolling-window kernel?)
     print(name, {k: "hip %.2e cpu %.2e" % v for k, v in res.items()})
     record("conv %s [%s%s%s]" % (name, ops.get_conv_compute_dtype(), ", bf16 tensors" if act16 else "", ", trained-like statistics" if trained else ""), res)
     return res

@@ -394,6 +394,34 @@ def test_conv_plan_reports_match_golden():
     assert not bad, "%d differences:\n%s" % (len(bad), "\n".join(bad[:40]))
 
 
+@pytest.mark.parametrize("mode", ["fp32x3", "fp32h2"])
+def test_resnet50_small_frame_table_keeps_the_200_frame_kernels(mode):
+    """tests/test_gpu_resnet50.py launches the 19 ResNet-50 convolutions at 5 ... 45 frames instead of 200 (tests/_r50_shapes.py); with
+    the forward / data-gradient tile pinned to the 200-frame launch's, lmkd_conv2d_plan must report the same tile, XCD tile order, parity
+    classes and kernel family as at 200 frames (weight gradient: tile, XCD order, family, no pin) - else the GPU test would anchor kernels
+    the benchmark does not run.  Pure host code."""
+    import litemkd_amd
+    import _r50_shapes as T
+    L = litemkd_amd.lib()
+    assert len(T.RESNET50) == 19
+    L.cdll.lmkd_conv_set_compute_dtype(T.MODES[mode])
+    try:
+        for shape in T.RESNET50:
+            N = T.frames(shape)
+            Ho = (shape[1] + 2 * shape[7] - shape[5]) // shape[6] + 1
+            assert N * Ho * Ho > 3 * 128 and (N * Ho * Ho) % 128 != 0, shape      # several row tiles, a ragged last one
+            T.assert_same_kernels(L, shape)
+        # the table reaches what the 200-frame ResNet-50 call runs and no ResNet-18 shape does: column-slice XCD order, the same-size
+        # 1x1 on the LDS-patch kernel in both 4-wave tiles, the XCD-grouped weight-gradient split of a 1x1
+        fwd = {s[0]: T.plan(L, 0, T.FULL, s) for s in T.RESNET50}
+        assert any(p[1] == 1 for p in fwd.values())
+        assert {11, 12} <= {p[0] for n, p in fwd.items() if p[4] == 1 and "3x3" not in n}, fwd
+        assert T.plan(L, 2, T.frames(T.RESNET50[13]), T.RESNET50[13])[1] == 1
+    finally:
+        L.cdll.lmkd_conv_set_compute_dtype(2)
+        L.cdll.lmkd_set_activation_dtype(0)
+
+
 def test_stream_registry_on_stand_in_streams(monkeypatch):
     """the one table of forked streams (ops: lane_main / side_stream / aux_stream / _wgrad_stream, lane_streams, forked_streams,
     stream_role, lane) with stand-in stream objects: no GPU involved"""
