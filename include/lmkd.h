@@ -341,6 +341,13 @@ int lmkd_trx_tuple_ln_fwd(const float* P, const float* bk, const float* bv, cons
                           float* Kn, float* Khat, float* V, float* rstd, int NV, int L, int D, float eps, void* stream); /* :85-104 */
 int lmkd_layernorm_bwd_rows(float* dK_inout, const float* Khat, const float* rstd, const float* gamma, long rows, int D, void* stream);
 int lmkd_trx_tuple_bwd_gather(const float* dKraw, const float* dV, const int* rowmap, float* dP, int NV, int L, int D, void* stream);
+/* the same two for frame tuples of cardinality card = 2 or 3 (TRX.py:51-73): P and dP are [NV*L, 2*card*D] =
+   [k_0 .. k_{card-1} | v_0 .. v_{card-1}], tuples a DEVICE int32 [T, card] table in itertools.combinations order, T = C(L, card) */
+int lmkd_trx_tuples_ln_fwd(const float* P, const float* bk, const float* bv, const float* gamma, const float* beta, const int* rowmap,
+                           const int* tuples, float* Kn, float* Khat, float* V, float* rstd, int NV, int L, int card, int T, int D,
+                           float eps, void* stream);
+int lmkd_trx_tuples_bwd_gather(const float* dKraw, const float* dV, const int* rowmap, const int* tuples, float* dP, int NV, int L,
+                               int card, int T, int D, void* stream);
 /* seg_off/seg_cnt/seg_col are HOST int arrays (<= 16 classes) */
 int lmkd_segment_softmax_fwd(float* S, long rows, long ld, int nseg, const int* seg_off, const int* seg_cnt, void* stream); /* :124-130 */
 int lmkd_segment_softmax_bwd(const float* P, float* dP_inout, long rows, long ld, int nseg, const int* seg_off, const int* seg_cnt,

@@ -2,9 +2,9 @@
 // Euclidean matcher that are not GEMMs.  All reductions are wavefront (64-lane) shuffles
 // + one LDS hop per 256-thread workgroup; results are deterministic.
 //
-// TRX data flow (host side in ops.py):  X -> (+PE, dropout) -> P = X * [Wk_a|Wk_b|Wv_a|Wv_b]^T
-//   (per-frame projections; the reference's 4096-wide tuple Linear is the sum of two 2048-wide
-//   halves) -> tuple combine + LayerNorm(K) -> scores GEMM -> per-class softmax -> P*V GEMM ->
+// TRX data flow (host side in ops.py):  X -> (+PE, dropout) -> P = X * [Wk_0|..|Wk_{c-1}|Wv_0|..|Wv_{c-1}]^T
+//   (per-frame projections; the reference's c*2048-wide tuple Linear, c = 2 frame pairs or 3 frame triples, is the
+//   sum of c 2048-wide slices) -> tuple combine + LayerNorm(K) -> scores GEMM -> per-class softmax -> P*V GEMM ->
 //   squared distance.
 #include "common.h"
 
@@ -108,10 +108,12 @@ extern "C" int lmkd_axpby(const float* x, float* y, float alpha, float beta, lon
 }
 
 // ---------------------------------------------------------------------------------
-// tuple combine + LayerNorm on keys.  P: [NV*L, 4*D] = [k_a | k_b | v_a | v_b] per frame.
-// tuple t = (i<j) in combinations(range(L),2) order.  Output row = rowmap[n]*T + t.
-//   Kraw = P[n,i].k_a + P[n,j].k_b + bk ; Khat = (Kraw-mean)*rstd ; Kn = Khat*gamma+beta
-//   V    = P[n,i].v_a + P[n,j].v_b + bv
+// tuple combine + LayerNorm on keys.  P: [NV*L, 2*CARD*D] = [k_0 .. k_{CARD-1} | v_0 .. v_{CARD-1}] per frame (the reference's
+// CARD*2048-wide tuple Linear is the sum of CARD 2048-wide per-frame slices).  tuple t = (f_0 < .. < f_{CARD-1}) in
+// combinations(range(L), CARD) order, read from the device table `tuples` [T, CARD]; without a table (pairs only) it is computed from t.
+// Output row = rowmap[n]*T + t.
+//   Kraw = ((P[n,f_0].k_0 + P[n,f_1].k_1) + P[n,f_2].k_2) + bk ; Khat = (Kraw-mean)*rstd ; Kn = Khat*gamma+beta
+//   V    = ((P[n,f_0].v_0 + P[n,f_1].v_1) + P[n,f_2].v_2) + bv
 // ---------------------------------------------------------------------------------
 __device__ __forceinline__ void tuple_ij(int t, int L, int& i, int& j) {
   int ii = 0, rem = t;
@@ -119,24 +121,34 @@ __device__ __forceinline__ void tuple_ij(int t, int L, int& i, int& j) {
   i = ii; j = ii + 1 + rem;
 }
 
-__global__ void trx_tuple_ln_fwd_kernel(const float* __restrict__ P, const float* __restrict__ bk, const float* __restrict__ bv,
-                                        const float* __restrict__ gamma, const float* __restrict__ beta, const int* __restrict__ rowmap,
-                                        float* __restrict__ Kn, float* __restrict__ Khat, float* __restrict__ V, float* __restrict__ rstd_out,
-                                        int L, int T, int D, float eps) {
+template <int CARD>
+__global__ void trx_tuples_ln_fwd_kernel(const float* __restrict__ P, const float* __restrict__ bk, const float* __restrict__ bv,
+                                         const float* __restrict__ gamma, const float* __restrict__ beta, const int* __restrict__ rowmap,
+                                         const int* __restrict__ tuples, float* __restrict__ Kn, float* __restrict__ Khat,
+                                         float* __restrict__ V, float* __restrict__ rstd_out, int L, int T, int D, float eps) {
   __shared__ float red[4];
   extern __shared__ float kraw[];  // D floats
   const int n = blockIdx.x / T, t = blockIdx.x % T;
-  int i, j;
-  tuple_ij(t, L, i, j);
-  const float* pi = P + (long)(n * L + i) * 4 * D;
-  const float* pj = P + (long)(n * L + j) * 4 * D;
+  int f[CARD];
+  if (tuples) {
+#pragma unroll
+    for (int s = 0; s < CARD; ++s) f[s] = tuples[t * CARD + s];
+  } else {      // CARD == 2 only (the host checks)
+    tuple_ij(t, L, f[0], f[CARD - 1]);
+  }
+  const float* pf[CARD];
+#pragma unroll
+  for (int s = 0; s < CARD; ++s) pf[s] = P + (long)(n * L + f[s]) * 2 * CARD * D;
   const long orow = (long)(rowmap ? rowmap[n] : n) * T + t;
   float s = 0.f;
   for (int d = threadIdx.x; d < D; d += TX_THREADS) {
-    const float k = pi[d] + pj[D + d] + bk[d];
+    float k = pf[0][d] + pf[1][D + d];
+    float v = pf[0][CARD * D + d] + pf[1][(CARD + 1) * D + d];
+    if (CARD == 3) { k += pf[CARD - 1][2 * D + d]; v += pf[CARD - 1][(CARD + 2) * D + d]; }
+    k += bk[d];
     kraw[d] = k;
     s += k;
-    V[orow * D + d] = pi[2 * D + d] + pj[3 * D + d] + bv[d];
+    V[orow * D + d] = v + bv[d];
   }
   const float mean = block_sum_256(s, red) / (float)D;
   float q = 0.f;
@@ -151,15 +163,41 @@ __global__ void trx_tuple_ln_fwd_kernel(const float* __restrict__ P, const float
   if (threadIdx.x == 0 && rstd_out) rstd_out[orow] = rstd;
 }
 
+static inline long n_choose(int L, int card) { return card == 2 ? (long)L * (L - 1) / 2 : (long)L * (L - 1) * (L - 2) / 6; }
+#define TX_MAX_TUPLES 4096      // the backward gather keeps the [T, CARD] table in LDS: 48 KB at most
+
+static int trx_tuples_ln_fwd_launch(const float* P, const float* bk, const float* bv, const float* gamma, const float* beta,
+                                    const int* rowmap, const int* tuples, float* Kn, float* Khat, float* V, float* rstd, int NV, int L,
+                                    int card, int T, int D, float eps, void* stream) {
+  const dim3 grid(NV * T), block(TX_THREADS);
+  const size_t lds = D * sizeof(float);
+  if (card == 2)
+    hipLaunchKernelGGL(trx_tuples_ln_fwd_kernel<2>, grid, block, lds, (hipStream_t)stream, P, bk, bv, gamma, beta, rowmap, tuples, Kn, Khat,
+                       V, rstd, L, T, D, eps);
+  else
+    hipLaunchKernelGGL(trx_tuples_ln_fwd_kernel<3>, grid, block, lds, (hipStream_t)stream, P, bk, bv, gamma, beta, rowmap, tuples, Kn, Khat,
+                       V, rstd, L, T, D, eps);
+  LMKD_CHECK_LAUNCH("trx_tuples_ln_fwd_kernel");
+  return LMKD_OK;
+}
+
+// pairs, tuple order computed in the kernel: the CARD = 2 instance without a table
 extern "C" int lmkd_trx_tuple_ln_fwd(const float* P, const float* bk, const float* bv, const float* gamma, const float* beta,
                                      const int* rowmap, float* Kn, float* Khat, float* V, float* rstd, int NV, int L, int D, float eps,
                                      void* stream) {
   LMKD_REQUIRE(P && bk && bv && gamma && beta && Kn && V && NV > 0 && L >= 2 && D > 0, "lmkd_trx_tuple_ln_fwd: bad arguments");
-  const int T = L * (L - 1) / 2;
-  hipLaunchKernelGGL(trx_tuple_ln_fwd_kernel, dim3(NV * T), dim3(TX_THREADS), D * sizeof(float), (hipStream_t)stream, P, bk, bv, gamma,
-                     beta, rowmap, Kn, Khat, V, rstd, L, T, D, eps);
-  LMKD_CHECK_LAUNCH("trx_tuple_ln_fwd_kernel");
-  return LMKD_OK;
+  return trx_tuples_ln_fwd_launch(P, bk, bv, gamma, beta, rowmap, nullptr, Kn, Khat, V, rstd, NV, L, 2, L * (L - 1) / 2, D, eps, stream);
+}
+
+extern "C" int lmkd_trx_tuples_ln_fwd(const float* P, const float* bk, const float* bv, const float* gamma, const float* beta,
+                                      const int* rowmap, const int* tuples, float* Kn, float* Khat, float* V, float* rstd, int NV, int L,
+                                      int card, int T, int D, float eps, void* stream) {
+  LMKD_REQUIRE(P && bk && bv && gamma && beta && Kn && V && NV > 0 && D > 0, "lmkd_trx_tuples_ln_fwd: bad arguments");
+  LMKD_REQUIRE(card == 2 || card == 3, "lmkd_trx_tuples_ln_fwd: cardinality %d (frame pairs and triples only)", card);
+  LMKD_REQUIRE(L >= card, "lmkd_trx_tuples_ln_fwd: %d frames for tuples of %d", L, card);
+  LMKD_REQUIRE(L <= 1024 && (long)T == n_choose(L, card), "lmkd_trx_tuples_ln_fwd: T = %d is not C(%d, %d)", T, L, card);
+  LMKD_REQUIRE(tuples, "lmkd_trx_tuples_ln_fwd: no tuple table");
+  return trx_tuples_ln_fwd_launch(P, bk, bv, gamma, beta, rowmap, tuples, Kn, Khat, V, rstd, NV, L, card, T, D, eps, stream);
 }
 
 // LayerNorm backward per row (in place: dKn -> dKraw):  dxh = dKn*gamma ;
@@ -189,30 +227,63 @@ extern "C" int lmkd_layernorm_bwd_rows(float* dK_inout, const float* Khat, const
   return LMKD_OK;
 }
 
-// dP[n*L+f] = [ sum_{t:i_t=f} dKraw | sum_{t:j_t=f} dKraw | sum_{t:i_t=f} dV | sum_{t:j_t=f} dV ]
-__global__ void trx_tuple_bwd_gather_kernel(const float* __restrict__ dKraw, const float* __restrict__ dV, const int* __restrict__ rowmap,
-                                            float* __restrict__ dP, int L, int T, int D) {
+// dP[n*L+f] = [ sum_{t: f_0(t)=f} dKraw | .. | sum_{t: f_{CARD-1}(t)=f} dKraw | the same sums of dV ], every sum in ascending t
+// (no atomics: one workgroup per (video, frame), the [T, CARD] table staged in LDS)
+template <int CARD>
+__global__ void trx_tuples_bwd_gather_kernel(const float* __restrict__ dKraw, const float* __restrict__ dV, const int* __restrict__ rowmap,
+                                             const int* __restrict__ tuples, float* __restrict__ dP, int L, int T, int D) {
+  extern __shared__ int tup[];  // T * CARD ints
+  if (tuples) {
+    for (int i = threadIdx.x; i < T * CARD; i += TX_THREADS) tup[i] = tuples[i];
+  } else {      // CARD == 2 only (the host checks)
+    for (int t = threadIdx.x; t < T; t += TX_THREADS) tuple_ij(t, L, tup[t * CARD], tup[t * CARD + CARD - 1]);
+  }
+  __syncthreads();
   const int n = blockIdx.x / L, f = blockIdx.x % L;
   const long base = (long)(rowmap ? rowmap[n] : n) * T;
-  float* o = dP + (long)blockIdx.x * 4 * D;
+  float* o = dP + (long)blockIdx.x * 2 * CARD * D;
   for (int d = threadIdx.x; d < D; d += TX_THREADS) {
-    float ka = 0.f, kb = 0.f, va = 0.f, vb = 0.f;
-    int t = 0;
-    for (int i = 0; i < L; ++i)
-      for (int j = i + 1; j < L; ++j, ++t) {
-        if (i == f) { ka += dKraw[(base + t) * D + d]; va += dV[(base + t) * D + d]; }
-        else if (j == f) { kb += dKraw[(base + t) * D + d]; vb += dV[(base + t) * D + d]; }
-      }
-    o[d] = ka; o[D + d] = kb; o[2 * D + d] = va; o[3 * D + d] = vb;
+    float k[CARD], v[CARD];
+#pragma unroll
+    for (int s = 0; s < CARD; ++s) { k[s] = 0.f; v[s] = 0.f; }
+    for (int t = 0; t < T; ++t) {
+#pragma unroll
+      for (int s = 0; s < CARD; ++s)
+        if (tup[t * CARD + s] == f) { k[s] += dKraw[(base + t) * D + d]; v[s] += dV[(base + t) * D + d]; }
+    }
+#pragma unroll
+    for (int s = 0; s < CARD; ++s) { o[s * D + d] = k[s]; o[(CARD + s) * D + d] = v[s]; }
   }
 }
+
+static int trx_tuples_bwd_gather_launch(const float* dKraw, const float* dV, const int* rowmap, const int* tuples, float* dP, int NV, int L,
+                                        int card, int T, int D, void* stream) {
+  const dim3 grid(NV * L), block(TX_THREADS);
+  const size_t lds = (size_t)T * card * sizeof(int);
+  if (card == 2)
+    hipLaunchKernelGGL(trx_tuples_bwd_gather_kernel<2>, grid, block, lds, (hipStream_t)stream, dKraw, dV, rowmap, tuples, dP, L, T, D);
+  else
+    hipLaunchKernelGGL(trx_tuples_bwd_gather_kernel<3>, grid, block, lds, (hipStream_t)stream, dKraw, dV, rowmap, tuples, dP, L, T, D);
+  LMKD_CHECK_LAUNCH("trx_tuples_bwd_gather_kernel");
+  return LMKD_OK;
+}
+
 extern "C" int lmkd_trx_tuple_bwd_gather(const float* dKraw, const float* dV, const int* rowmap, float* dP, int NV, int L, int D,
                                          void* stream) {
   LMKD_REQUIRE(dKraw && dV && dP && NV > 0 && L >= 2, "lmkd_trx_tuple_bwd_gather: bad arguments");
-  hipLaunchKernelGGL(trx_tuple_bwd_gather_kernel, dim3(NV * L), dim3(TX_THREADS), 0, (hipStream_t)stream, dKraw, dV, rowmap, dP, L,
-                     L * (L - 1) / 2, D);
-  LMKD_CHECK_LAUNCH("trx_tuple_bwd_gather_kernel");
-  return LMKD_OK;
+  LMKD_REQUIRE(n_choose(L, 2) <= TX_MAX_TUPLES, "lmkd_trx_tuple_bwd_gather: more than %d frame pairs", TX_MAX_TUPLES);
+  return trx_tuples_bwd_gather_launch(dKraw, dV, rowmap, nullptr, dP, NV, L, 2, L * (L - 1) / 2, D, stream);
+}
+
+extern "C" int lmkd_trx_tuples_bwd_gather(const float* dKraw, const float* dV, const int* rowmap, const int* tuples, float* dP, int NV,
+                                          int L, int card, int T, int D, void* stream) {
+  LMKD_REQUIRE(dKraw && dV && dP && NV > 0 && D > 0, "lmkd_trx_tuples_bwd_gather: bad arguments");
+  LMKD_REQUIRE(card == 2 || card == 3, "lmkd_trx_tuples_bwd_gather: cardinality %d (frame pairs and triples only)", card);
+  LMKD_REQUIRE(L >= card, "lmkd_trx_tuples_bwd_gather: %d frames for tuples of %d", L, card);
+  LMKD_REQUIRE(L <= 1024 && (long)T == n_choose(L, card), "lmkd_trx_tuples_bwd_gather: T = %d is not C(%d, %d)", T, L, card);
+  LMKD_REQUIRE(T <= TX_MAX_TUPLES, "lmkd_trx_tuples_bwd_gather: more than %d tuples", TX_MAX_TUPLES);
+  LMKD_REQUIRE(tuples, "lmkd_trx_tuples_bwd_gather: no tuple table");
+  return trx_tuples_bwd_gather_launch(dKraw, dV, rowmap, tuples, dP, NV, L, card, T, D, stream);
 }
 
 // ---------------------------------------------------------------------------------

@@ -19,8 +19,8 @@ from .utils import aggregate_accuracy
 
 
 def select_test(args):
-    """model_select.py:244-260.  'teacher': TRX_fixed with the `bracnch.transformers.0.*` weights of an MFM checkpoint
-    (load_teacher); 'student': the checkpoint written by the training loop (load_student; commented out in the reference's
+    """model_select.py:244-260.  'teacher': TRX_fixed with the `bracnch.transformers.<i>.*` weights of an MFM checkpoint, one entry
+    per cardinality of args.temp_set (load_teacher); 'student': the checkpoint written by the training loop (load_student; commented out in the reference's
     dict although test.py:103-104 evaluates it)."""
     name2test = {
         "teacher": lambda: load_teacher(classifiers.TRX_fixed(args), args),
@@ -85,6 +85,7 @@ def main(argv=None):
     ap.add_argument("--traintestlist", default=None, help="directory of the split lists {train,test}list<split>.txt")
     ap.add_argument("--teacher_path", default=None, help="teacher features <teacher_path>/<class>/<video>/<file>.npy (--test_model teacher)")
     ap.add_argument("--split", type=int, default=getattr(base, "split", 3))
+    ap.add_argument("--temp_set", nargs="+", type=int, default=list(base.temp_set), help="cardinalities e.g. 2,3 is pairs and triples")
     ap.add_argument("--seed", type=int, default=0)
     a = ap.parse_args(argv)
     kw = {k: v for k, v in vars(a).items() if k not in ("rgb_path", "traintestlist", "teacher_path", "seed")}

@@ -3,7 +3,12 @@
 Differences from the reference that do not change results: logits stay on the device (the
 reference assembles them in CPU tensors, :114,180, and the distiller moves them back); the
 4096-wide tuple Linear is evaluated as two 2048-wide per-frame projections (same sum, 3.5x fewer
-FLOPs); all classes are matched in one pass over class-sorted support tuples."""
+FLOPs; frame triples: three of the 6144-wide Linear's); all classes are matched in one pass over class-sorted support tuples.
+
+Cardinalities: `args.temp_set` lists the frame-tuple sizes of a head, as the teacher head TrxBranch reads it (teacher/code/model.py:
+1094-1128).  [2] (the default, also when the attribute is missing) is the reference's student: ONE module under `transformers.*`.  A
+single other entry gives one module of that cardinality under the same keys; several entries give `transformers` as an nn.ModuleList
+(keys `transformers.<i>.*`, the layout of `bracnch.transformers.<i>.*`) whose logits are averaged."""
 import math
 
 import torch
@@ -35,8 +40,8 @@ class TemporalCrossTransformer(nn.Module):
 
     def __init__(self, args, temporal_set_size=2):
         super().__init__()
-        if temporal_set_size != 2:
-            raise NotImplementedError("only frame pairs (temporal_set_size=2) are on the hot path")
+        if temporal_set_size not in (2, 3):
+            raise NotImplementedError("only frame pairs and triples (temporal_set_size 2 or 3) are on the hot path")
         self.args = args
         self.temporal_set_size = temporal_set_size
         max_len = int(self.args.seq_len * 1.5)
@@ -45,7 +50,7 @@ class TemporalCrossTransformer(nn.Module):
         self.v_linear = nn.Linear(2048 * temporal_set_size, self.args.trans_linear_out_dim)
         self.norm_k = nn.LayerNorm(self.args.trans_linear_out_dim)
         self.norm_v = nn.LayerNorm(self.args.trans_linear_out_dim)       # unused by forward (:106), as in the reference
-        self.tuples_len = self.args.seq_len * (self.args.seq_len - 1) // 2
+        self.tuples_len = math.comb(self.args.seq_len, temporal_set_size)      # TRX.py:70-73: combinations(range(seq_len), size)
 
     @staticmethod
     def draw_dropout_seed():
@@ -86,6 +91,45 @@ class TemporalCrossTransformer(nn.Module):
         return {"logits": logits}
 
 
+def temp_set_of(args):
+    """args.temp_set -> list of cardinalities; a missing attribute means [2].  Values outside {2, 3} and repeats raise ValueError."""
+    ts = getattr(args, "temp_set", None)
+    if ts is None:
+        return [2]
+    ts = [ts] if isinstance(ts, int) else list(ts)
+    if not ts or any(not isinstance(v, int) or isinstance(v, bool) or v not in (2, 3) for v in ts):
+        raise ValueError("temp_set %r: the frame-tuple cardinalities are 2 (pairs) and 3 (triples)" % (ts,))
+    if len(set(ts)) != len(ts):
+        raise ValueError("temp_set %r repeats a cardinality" % (ts,))
+    return ts
+
+
+def build_transformers(args):
+    """-> one TemporalCrossTransformer (a single cardinality: the reference students' `transformers.*` keys) or an nn.ModuleList with
+    one per entry of args.temp_set (TrxBranch, teacher/code/model.py:1106-1107: `transformers.<i>.*`)"""
+    ts = temp_set_of(args)
+    if len(ts) == 1:
+        return TemporalCrossTransformer(args, ts[0])
+    return nn.ModuleList([TemporalCrossTransformer(args, s) for s in ts])
+
+
+def single_transformer(args, plugin):
+    """TRX_sup.py defines its prototype similarity for one tuple set: one cardinality, 2 or 3"""
+    ts = temp_set_of(args)
+    if len(ts) != 1:
+        raise NotImplementedError("classifier plugin '%s' takes one cardinality (temp_set %r): the reference defines no prototype "
+                                  "similarity across cardinalities" % (plugin, ts))
+    return TemporalCrossTransformer(args, ts[0])
+
+
+def head_logits(transformers, support_set, support_labels, queries):
+    """logits [Nq, way] of one head: the module's, or the mean over the cardinalities of a ModuleList (model.py:1117-1123).  Every
+    module draws its own dropout mask, as every reference module owns its nn.Dropout."""
+    if not isinstance(transformers, nn.ModuleList):
+        return transformers(support_set, support_labels, queries)["logits"]
+    return torch.stack([t(support_set, support_labels, queries)["logits"] for t in transformers], dim=-1).mean(dim=-1)
+
+
 class SupportDK(nn.Module):
     """TRX_2fcsup.py:162-189 (== e_dist_fc2.py:17-44).  Ignores the labels and assumes class-sorted
     support, exactly like the reference; output is [5,4] (way x way-1)."""
@@ -105,29 +149,29 @@ class TRX_2fcsup(nn.Module):
         super().__init__()
         self.train()
         self.args = args
-        self.transformers = TemporalCrossTransformer(args, 2)
+        self.transformers = build_transformers(args)
         self.supportKD = SupportDK(args)
 
     def forward(self, context_feature, context_labels, target_feature):
         c1, t1 = context_feature["context_features_1"], target_feature["target_features_1"]
         c2, t2 = context_feature["context_features_2"], target_feature["target_features_2"]
-        l1 = self.transformers(c1, context_labels, t1)["logits"]
+        l1 = head_logits(self.transformers, c1, context_labels, t1)
         if ops.HEADS_ON_TWO_STREAMS and c2.is_cuda:
             # the 'ce' head does not depend on the 'kl' head: its ~20 small GEMM / softmax launches (126 workgroups each on a 256-CU
             # chip) run on the auxiliary stream beside the first head's, forward and - autograd replays a node on the stream of its
-            # forward - backward
+            # forward - backward.  With several cardinalities each head runs all of its on its own stream.
             main, aux = torch.cuda.current_stream(c2.device), ops.aux_stream(c2.device)
             ops.get_plan(context_labels, self.args.way).full_rowmap(c2.shape[0] + t2.shape[0])      # shared per-episode tensors: made on main
             aux.wait_stream(main)
             with torch.cuda.stream(aux):
-                l2 = self.transformers(c2, context_labels, t2)["logits"]
+                l2 = head_logits(self.transformers, c2, context_labels, t2)
             for t in (c2, t2):
                 t.record_stream(aux)
             l3 = self.supportKD(c2, context_labels, t2)["logits"]
             main.wait_stream(aux)
             l2.record_stream(main)
         else:
-            l2 = self.transformers(c2, context_labels, t2)["logits"]
+            l2 = head_logits(self.transformers, c2, context_labels, t2)
             l3 = self.supportKD(c2, context_labels, t2)["logits"]
         return {"logits": {"kl": l1, "ce": l2, "sup": l3}}
 
@@ -139,12 +183,12 @@ class TRX_2fcsup_fixed(nn.Module):
         super().__init__()
         self.train()
         self.args = args
-        self.transformers = TemporalCrossTransformer(args, 2)
+        self.transformers = build_transformers(args)
         self.supportKD = SupportDK(args)
 
     def forward(self, context_feature, context_labels, target_feature):
         with torch.no_grad():
-            l1 = self.transformers(context_feature, context_labels, target_feature)["logits"]
+            l1 = head_logits(self.transformers, context_feature, context_labels, target_feature)
             l2 = self.supportKD(context_feature, context_labels, target_feature)["logits"]
         return {"logits": {"kl": l1, "sup": l2}}
 
@@ -156,10 +200,10 @@ class TRX(nn.Module):
         super().__init__()
         self.train()
         self.args = args
-        self.transformers = TemporalCrossTransformer(args, 2)
+        self.transformers = build_transformers(args)
 
     def forward(self, context_feature, context_labels, target_feature):
-        return self.transformers(context_feature, context_labels, target_feature)
+        return {"logits": head_logits(self.transformers, context_feature, context_labels, target_feature)}
 
 
 class TRX_fixed(nn.Module):
@@ -169,14 +213,14 @@ class TRX_fixed(nn.Module):
         super().__init__()
         self.train()
         self.args = args
-        self.transformers = TemporalCrossTransformer(args, 2)
+        self.transformers = build_transformers(args)
 
     def forward(self, context_feature, context_labels, target_feature):
         with torch.no_grad():
             L, D = self.args.seq_len, self.args.trans_linear_in_dim
             c = context_feature.reshape(-1, L, D)
             t = target_feature.reshape(-1, L, D)
-            return {"logits": self.transformers(c, context_labels, t)["logits"]}
+            return {"logits": head_logits(self.transformers, c, context_labels, t)}
 
 
 class TRX_sup(nn.Module):
@@ -187,7 +231,7 @@ class TRX_sup(nn.Module):
         super().__init__()
         self.train()
         self.args = args
-        self.transformers = TemporalCrossTransformer(args, 2)
+        self.transformers = single_transformer(args, "TRX_sup")
 
     def forward(self, context_feature, context_labels, target_feature):
         return self.transformers(context_feature, context_labels, target_feature, with_sim=True)
@@ -200,7 +244,7 @@ class TRX_sup_fixed(nn.Module):
         super().__init__()
         self.train()
         self.args = args
-        self.transformers = TemporalCrossTransformer(args, 2)
+        self.transformers = single_transformer(args, "TRX_sup_fixed")
 
     def forward(self, context_feature, context_labels, target_feature):
         with torch.no_grad():
@@ -214,9 +258,9 @@ class TRX_2fc(nn.Module):
         super().__init__()
         self.train()
         self.args = args
-        self.transformers = TemporalCrossTransformer(args, 2)
+        self.transformers = build_transformers(args)
 
     def forward(self, context_feature, context_labels, target_feature):
-        l1 = self.transformers(context_feature["context_features_1"], context_labels, target_feature["target_features_1"])["logits"]
-        l2 = self.transformers(context_feature["context_features_2"], context_labels, target_feature["target_features_2"])["logits"]
+        l1 = head_logits(self.transformers, context_feature["context_features_1"], context_labels, target_feature["target_features_1"])
+        l2 = head_logits(self.transformers, context_feature["context_features_2"], context_labels, target_feature["target_features_2"])
         return {"logits": {"fc_1": l1, "fc_2": l2}}

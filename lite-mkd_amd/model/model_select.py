@@ -95,15 +95,23 @@ def select_model_teacher(args):
 
 
 def load_teacher(teacher, args):
-    """model_select.py:81-136: copy `bracnch.transformers.0.*` of an MFM checkpoint into the teacher TRX."""
+    """model_select.py:81-136: copy `bracnch.transformers.<i>.*` of an MFM checkpoint into the teacher TRX - entry 0 into a single
+    module (the reference copies that one), entry i into module i of a head built with several cardinalities (args.temp_set).  A
+    checkpoint with fewer entries than the head raises KeyError naming the first missing key."""
     sd = torch.load(args.teacher_checkpoint, map_location="cpu")["model_state_dict"]
-    t = teacher.transformers
-    pre = "bracnch.transformers.0."
+    mods = list(teacher.transformers) if isinstance(teacher.transformers, nn.ModuleList) else [teacher.transformers]
+
+    def entry(key):
+        if key not in sd:
+            raise KeyError("teacher checkpoint %s has no '%s' (the head has %d cardinalities)" % (args.teacher_checkpoint, key, len(mods)))
+        return sd[key]
     with torch.no_grad():
-        t.pe.pe.copy_(sd[pre + "pe.pe"])
-        for mod, name in ((t.k_linear, "k_linear"), (t.v_linear, "v_linear"), (t.norm_k, "norm_k"), (t.norm_v, "norm_v")):
-            mod.weight.copy_(sd[pre + name + ".weight"])
-            mod.bias.copy_(sd[pre + name + ".bias"])
+        for i, t in enumerate(mods):
+            pre = "bracnch.transformers.%d." % i
+            t.pe.pe.copy_(entry(pre + "pe.pe"))
+            for mod, name in ((t.k_linear, "k_linear"), (t.v_linear, "v_linear"), (t.norm_k, "norm_k"), (t.norm_v, "norm_v")):
+                mod.weight.copy_(entry(pre + name + ".weight"))
+                mod.bias.copy_(entry(pre + name + ".bias"))
     return teacher
 
 

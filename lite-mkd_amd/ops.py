@@ -5,6 +5,7 @@ graph); all arithmetic of the hot path happens in liblmkd_hip.so.
 Activations are NHWC fp32.  Every wrapper checks device/dtype/contiguity and raises on misuse."""
 import ctypes
 import os
+import itertools
 import math
 
 import torch
@@ -2058,6 +2059,7 @@ class ClassPlan:
         self._tail = tail
         self.uniform = len(set(self.counts)) == 1
         self._full = {}
+        self._pos = pos
 
     def full_rowmap(self, nv):
         """support rows class-sorted, query rows in place: [Ns + Nq] int32 - a view of the plan's single upload (no launch) while
@@ -2070,8 +2072,25 @@ class ClassPlan:
                 self._full[nv] = torch.cat([self.rowmap, torch.arange(self.ns, nv, dtype=torch.int32, device=self.rowmap.device)])
         return self._full[nv]
 
+    def padded_rowmap(self, nv, slots):
+        """full_rowmap with class s given slots[s] >= counts[s] video positions (the unused ones stay empty): [Ns + Nq] int32, queries
+        after sum(slots).  One small upload per (nv, slots), made on the current stream."""
+        key = (nv, tuple(slots))
+        if key not in self._full:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("the padded class layout of this episode must exist before a hipGraph capture: run the episode eagerly first")
+            to_pad, start, p_ = {}, 0, 0
+            for c, sl in zip(self.counts, slots):
+                for j in range(c):
+                    to_pad[p_ + j] = start + j
+                p_, start = p_ + c, start + sl
+            pos = [to_pad[p] for p in self._pos] + list(range(start, start + nv - self.ns))
+            self._full[key] = h2d_async(torch.tensor(pos, dtype=torch.int32), self.device)
+        return self._full[key]
 
-# The four projections of a TRX head, P = Xp @ [Wk[:, :Din] | Wk[:, Din:] | Wv[:, :Din] | Wv[:, Din:]]^T (400 x 4608 x 2048), and their
+
+# The 2 * card projections of a TRX head (card = 2 frame pairs, 3 frame triples: 6912 columns), for pairs
+# P = Xp @ [Wk[:, :Din] | Wk[:, Din:] | Wv[:, :Din] | Wv[:, Din:]]^T (400 x 4608 x 2048), and their
 # input gradient dXp = dP @ Wcat are 1x1 convolutions over 400 one-pixel frames: in the three-plane arithmetic (the library default)
 # they run the bf16-plane patch kernel - ONE launch of 288 (forward) / 128 (input gradient) workgroups at the convolutions' rate
 # instead of 2 + 4 launches of the fp32-MFMA GEMM at 50 - 64 TFLOP/s.  Wcat's fragment-order planes are cached per (Wk, Wv) and rebuilt
@@ -2084,9 +2103,10 @@ _WCAT = {}
 
 
 def _wcat_build(e, wk, wv):
-    D, Din = wk.shape[0], wk.shape[1] // 2
-    torch.cat([wk.detach()[:, :Din], wk.detach()[:, Din:], wv.detach()[:, :Din], wv.detach()[:, Din:]], 0, out=e["cat"])
-    w4 = e["cat"].view(4 * D, Din, 1, 1)
+    card = e.get("card", 2)
+    D, Din = wk.shape[0], wk.shape[1] // card
+    torch.cat([w.detach()[:, s * Din:(s + 1) * Din] for w in (wk, wv) for s in range(card)], 0, out=e["cat"])
+    w4 = e["cat"].view(2 * card * D, Din, 1, 1)
     e["p0"] = _pack_weights(w4, Din, 0, out=e.get("p0"))
     e["p1"] = _pack_weights(w4, Din, 1, out=e.get("p1"))
     e["tag"] = (wk._version, wv._version, WEIGHT_EPOCH[0])
@@ -2115,19 +2135,21 @@ def _x3_scope():
         set_activation_dtype(act)
 
 
-def _trx_wcat_packs(wk, wv):
-    """-> (forward planes, data-gradient planes) of the concatenated projection weight as a [4D, Din, 1, 1] convolution weight, or None
-    when the projections stay on the GEMM (native fp32 mode, odd sizes).  Call inside _x3_scope()."""
+def _trx_wcat_packs(wk, wv, card=2):
+    """-> (forward planes, data-gradient planes) of the concatenated projection weight as a [2*card*D, Din, 1, 1] convolution weight, or
+    None when the projections stay on the GEMM (native fp32 mode, odd sizes).  Call inside _x3_scope()."""
     cd = lib().value("lmkd_conv_get_compute_dtype")
     D, K2 = wk.shape
-    if not TRX_PROJ_ON_CONV or cd not in (2, 3) or _ACT_DTYPE[0] is not torch.float32 or K2 % 64 != 0 or D % 32 != 0 or wv.shape != wk.shape:
+    if (not TRX_PROJ_ON_CONV or cd not in (2, 3) or _ACT_DTYPE[0] is not torch.float32 or K2 % (32 * card) != 0 or D % 32 != 0
+            or wv.shape != wk.shape):
         return None
     key = (wk.data_ptr(), wv.data_ptr(), cd)
     e = _WCAT.get(key)
     if e is None or e["rk"]() is not wk or e["rv"]() is not wv:
         if len(_WCAT) > 16:
             _WCAT.clear()
-        e = _WCAT[key] = {"rk": weakref.ref(wk), "rv": weakref.ref(wv), "cat": torch.empty((4 * D, K2 // 2), dtype=torch.float32, device=wk.device)}
+        e = _WCAT[key] = {"rk": weakref.ref(wk), "rv": weakref.ref(wv), "card": card,
+                          "cat": torch.empty((2 * card * D, K2 // card), dtype=torch.float32, device=wk.device)}
         _wcat_build(e, wk, wv)
     elif e["tag"] != (wk._version, wv._version, WEIGHT_EPOCH[0]):
         _wcat_build(e, wk, wv)
@@ -2136,50 +2158,101 @@ def _trx_wcat_packs(wk, wv):
     return e["p0"], e["p1"]
 
 
+_TUPLE_TABLES = {}
+
+
+def trx_tuple_table(L, card, device):
+    """device int32 [C(L, card), card]: the frame tuples in itertools.combinations order (TRX.py:70-72).  One tensor per (L, card,
+    device) for the life of the process - never freed, a captured hipGraph holds its address.  The upload is synchronous (made by the
+    first eager episode, before any capture), so every stream may read the table afterwards."""
+    device = torch.device(device)
+    key = (L, card, device.index if device.index is not None else torch.cuda.current_device())
+    t = _TUPLE_TABLES.get(key)
+    if t is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("the frame-tuple table for (%d frames, cardinality %d) must exist before a hipGraph capture: run one eager episode first" % (L, card))
+        t = _TUPLE_TABLES[key] = torch.tensor(list(itertools.combinations(range(L), card)), dtype=torch.int32).reshape(-1, card).to(device)
+    return t
+
+
+def _trx_card(wk, wv, Din, L):
+    """cardinality of the frame tuples, from the width of the tuple Linear (TRX.py:61-62): 2 or 3"""
+    card, rest = divmod(wk.shape[1], Din)
+    if rest or card not in (2, 3) or wv.shape != wk.shape:
+        raise RuntimeError("TRX: k_linear %s / v_linear %s do not take 2 or 3 frames of %d features" % (tuple(wk.shape), tuple(wv.shape), Din))
+    if L < card:
+        raise RuntimeError("TRX: %d frames per video, tuples of %d" % (L, card))
+    return card
+
+
+def _trx_class_slots(counts, T):
+    """video positions per class in the class-sorted tuple rows: the class's own count, raised until count * T is a multiple of 4 (the
+    GEMMs over one class's rows read float4 along them).  8 frames: T = 28 or 56, nothing is ever added; 4 frames, pairs (T = 6): an odd
+    shot count takes one empty position, whose key / value rows are zero and lie outside the class's softmax segment - they add nothing
+    to any product."""
+    out = []
+    for c in counts:
+        while (c * T) % 4:
+            c += 1
+        out.append(c)
+    return out
+
+
 def _trx_forward(sup, qry, plan, wk, bk, wv, bv, gamma, beta, pe, mask, want_grad):
     """Shared by the student heads (with grad) and the frozen teacher head.
     sup [Ns,L,2048], qry [Nq,L,2048] -> logits [Nq,way] (+ saved tensors)"""
     Ns, L, Din = sup.shape
     Nq = qry.shape[0]
     D = wk.shape[0]
-    T = L * (L - 1) // 2
+    card = _trx_card(wk, wv, Din, L)
+    T = math.comb(L, card)
     NV = Ns + Nq
     X = stack_rows(sup.reshape(Ns * L, Din), qry.reshape(Nq * L, Din))      # (the fc head's output halves: a view, no copy)
     Xp = torch.empty_like(X)
     lib().call("lmkd_add_pe", _p(X), _p(pe), _p(mask), _p(Xp), NV * L, Din, L, _stream())
-    # per-frame projections: P = Xp @ [Wk[:, :Din] | Wk[:, Din:] | Wv[:, :Din] | Wv[:, Din:]]^T
-    P = _empty((NV * L, 4 * D), X)
+    # per-frame projections: P = Xp @ [Wk[:, slot 0] | .. | Wk[:, slot card-1] | Wv[:, slot 0] | .. | Wv[:, slot card-1]]^T
+    PW = 2 * card * D
+    P = _empty((NV * L, PW), X)
     packs = None
     if TRX_PROJ_ON_CONV:
         with _x3_scope():
-            packs = _trx_wcat_packs(wk, wv)
+            packs = _trx_wcat_packs(wk, wv, card)
             if packs is not None:
-                lib().call("lmkd_conv2d_fwd", _p(Xp), _p(packs[0]), _p(P), None, NV * L, 1, 1, Din, 4 * D, 1, 1, 1, 0, _stream())
+                lib().call("lmkd_conv2d_fwd", _p(Xp), _p(packs[0]), _p(P), None, NV * L, 1, 1, Din, PW, 1, 1, 1, 0, _stream())
     if packs is None:
-        gemm("K", "K", NV * L, D, Din, Xp, Din, wk, 2 * Din, P, 4 * D, batch=2, sB=Din, sC=D)
-        gemm("K", "K", NV * L, D, Din, Xp, Din, wv, 2 * Din, P, 4 * D, batch=2, sB=Din, sC=D, C_off=2 * D)
-    rowmap = plan.full_rowmap(NV)
-    Kn = _empty((NV * T, D), X)
-    V = _empty((NV * T, D), X)
-    Khat = _empty((NV * T, D), X) if want_grad else None
-    rstd = _empty((NV * T,), X) if want_grad else None
-    lib().call("lmkd_trx_tuple_ln_fwd", _p(P), _p(bk), _p(bv), _p(gamma), _p(beta), _p(rowmap), _p(Kn), _p(Khat), _p(V),
-               _p(rstd), NV, L, D, _f32(1e-5), _stream())
-    Rs, Rq = Ns * T, Nq * T
+        gemm("K", "K", NV * L, D, Din, Xp, Din, wk, card * Din, P, PW, batch=card, sB=Din, sC=D)
+        gemm("K", "K", NV * L, D, Din, Xp, Din, wv, card * Din, P, PW, batch=card, sB=Din, sC=D, C_off=card * D)
+    slots = _trx_class_slots(plan.counts, T)
+    padded = slots != plan.counts
+    NsP = sum(slots)
+    rowmap = plan.padded_rowmap(NV, slots) if padded else plan.full_rowmap(NV)
+    alloc = (lambda shape, like: torch.zeros(shape, dtype=torch.float32, device=like.device)) if padded else _empty
+    Kn = alloc(((NsP + Nq) * T, D), X)
+    V = alloc(((NsP + Nq) * T, D), X)
+    Khat = alloc(((NsP + Nq) * T, D), X) if want_grad else None
+    rstd = alloc(((NsP + Nq) * T,), X) if want_grad else None
+    if card == 2:
+        lib().call("lmkd_trx_tuple_ln_fwd", _p(P), _p(bk), _p(bv), _p(gamma), _p(beta), _p(rowmap), _p(Kn), _p(Khat), _p(V),
+                   _p(rstd), NV, L, D, _f32(1e-5), _stream())
+    else:
+        lib().call("lmkd_trx_tuples_ln_fwd", _p(P), _p(bk), _p(bv), _p(gamma), _p(beta), _p(rowmap), _p(trx_tuple_table(L, card, X.device)),
+                   _p(Kn), _p(Khat), _p(V), _p(rstd), NV, L, card, T, D, _f32(1e-5), _stream())
+    Rs, Rq = NsP * T, Nq * T
     Sk, Sv = Kn[:Rs], V[:Rs]
     Qk, Qv = Kn[Rs:], V[Rs:]
     S = _empty((Rq, Rs), X)
     gemm("K", "K", Rq, Rs, D, Qk, D, Sk, D, S, Rs, alpha=1.0 / math.sqrt(D))
     nseg = len(plan.classes)
-    seg_cnt = [c * T for c in plan.counts]
-    seg_off = [sum(seg_cnt[:i]) for i in range(nseg)]
+    seg_cnt = [c * T for c in plan.counts]      # the class's own tuple rows: its softmax segment
+    seg_k = [c * T for c in slots]              # rows the class occupies (== seg_cnt unless padded)
+    seg_off = [sum(seg_k[:i]) for i in range(nseg)]
     lib().call("lmkd_segment_softmax_fwd", _p(S), Rq, Rs, nseg, _ints(seg_off), _ints(seg_cnt), _stream())
     proto = _empty((nseg, Rq, D), X)
     if plan.uniform:
-        gemm("K", "N", Rq, D, seg_cnt[0], S, Rs, Sv, D, proto, D, batch=nseg, sA=seg_cnt[0], sB=seg_cnt[0] * D, sC=Rq * D)
+        gemm("K", "N", Rq, D, seg_k[0], S, Rs, Sv, D, proto, D, batch=nseg, sA=seg_k[0], sB=seg_k[0] * D, sC=Rq * D)
     else:
         for s in range(nseg):
-            gemm("K", "N", Rq, D, seg_cnt[s], S, Rs, Sv, D, proto, D, A_off=seg_off[s], B_off=seg_off[s] * D, C_off=s * Rq * D)
+            gemm("K", "N", Rq, D, seg_k[s], S, Rs, Sv, D, proto, D, A_off=seg_off[s], B_off=seg_off[s] * D, C_off=s * Rq * D)
     logits = torch.zeros((Nq, plan.way), dtype=torch.float32, device=X.device)
     lib().call("lmkd_trx_dist_fwd", _p(Qv), _p(proto), _p(logits), Nq, plan.way, T, D, nseg, _ints(plan.classes), _stream())
     saved = (Xp, Kn, V, Khat, rstd, S, proto, rowmap, seg_off, seg_cnt)
@@ -2213,13 +2286,18 @@ def _trx_backward(ctx, g, gsim=None, gram=None):
         plan, seg_off, seg_cnt = ctx.plan, ctx.seg_off, ctx.seg_cnt
         (Ns, L, Din), (Nq, _, _) = ctx.shapes
         D = wk.shape[0]
-        T = L * (L - 1) // 2
-        NV, Rs, Rq = Ns + Nq, Ns * T, Nq * T
+        card = wk.shape[1] // Din
+        T = math.comb(L, card)
+        PW = 2 * card * D
+        slots = _trx_class_slots(plan.counts, T)      # (see _trx_forward: empty video positions, all-zero rows)
+        seg_k = [c * T for c in slots]
+        NV, Rs, Rq = Ns + Nq, sum(slots) * T, Nq * T
+        rows = Rs + Rq
         nseg = len(plan.classes)
         g = g.contiguous()
         Sk, Sv, Qk, Qv = Kn[:Rs], V[:Rs], Kn[Rs:], V[Rs:]
-        dKn = _empty((NV * T, D), Xp)
-        dV = _empty((NV * T, D), Xp)
+        dKn = _empty((rows, D), Xp)
+        dV = _empty((rows, D), Xp)
         dSk, dSv, dQk, dQv = dKn[:Rs], dV[:Rs], dKn[Rs:], dV[Rs:]
         dp_sim = None
         if gsim is not None:      # needs the prototypes themselves: before they are overwritten below
@@ -2232,12 +2310,12 @@ def _trx_backward(ctx, g, gsim=None, gram=None):
             lib().call("lmkd_axpby", _p(dp_sim), _p(proto), _f32(1.0), _f32(1.0), proto.numel(), _stream())
         dS = _empty((Rq, Rs), Xp)
         if plan.uniform:
-            c = seg_cnt[0]
+            c = seg_k[0]
             gemm("K", "K", Rq, c, D, proto, D, Sv, D, dS, Rs, batch=nseg, sA=Rq * D, sB=c * D, sC=c)        # dP = dproto @ Vc^T
             gemm("M", "N", c, D, Rq, S, Rs, proto, D, dSv, D, batch=nseg, sA=c, sB=Rq * D, sC=c * D)       # dVc = P^T @ dproto
         else:
             for s in range(nseg):
-                c, o = seg_cnt[s], seg_off[s]
+                c, o = seg_k[s], seg_off[s]
                 gemm("K", "K", Rq, c, D, proto, D, Sv, D, dS, Rs, A_off=s * Rq * D, B_off=o * D, C_off=o)
                 gemm("M", "N", c, D, Rq, S, Rs, proto, D, dSv, D, A_off=o, B_off=s * Rq * D, C_off=o * D)
         lib().call("lmkd_segment_softmax_bwd", _p(S), _p(dS), Rq, Rs, nseg, _ints(seg_off), _ints(seg_cnt), _stream())
@@ -2256,36 +2334,40 @@ def _trx_backward(ctx, g, gsim=None, gram=None):
         # LayerNorm parameter grads, then dKn -> dKraw in place
         dgamma = colsum_into(gamma, dKn, Khat)
         dbeta = colsum_into(beta_, dKn)
-        lib().call("lmkd_layernorm_bwd_rows", _p(dKn), _p(Khat), _p(rstd), _p(gamma), NV * T, D, _stream())
+        lib().call("lmkd_layernorm_bwd_rows", _p(dKn), _p(Khat), _p(rstd), _p(gamma), rows, D, _stream())
         dbk = colsum_into(bk_, dKn)
         dbv = colsum_into(bv_, dV)
-        dP = _empty((NV * L, 4 * D), Xp)
-        lib().call("lmkd_trx_tuple_bwd_gather", _p(dKn), _p(dV), _p(rowmap), _p(dP), NV, L, D, _stream())
-        # weight grads: dW[:, half] = dP[:, blk]^T @ Xp
+        dP = _empty((NV * L, PW), Xp)
+        if card == 2:
+            lib().call("lmkd_trx_tuple_bwd_gather", _p(dKn), _p(dV), _p(rowmap), _p(dP), NV, L, D, _stream())
+        else:
+            lib().call("lmkd_trx_tuples_bwd_gather", _p(dKn), _p(dV), _p(rowmap), _p(trx_tuple_table(L, card, Xp.device)), _p(dP), NV, L,
+                       card, T, D, _stream())
+        # weight grads: dW[:, slot] = dP[:, blk]^T @ Xp
         dwk = dwv = None
-        if not side_accumulate(wk, lambda t: gemm("M", "N", D, Din, NV * L, dP, 4 * D, Xp, Din, t, 2 * Din, batch=2, sA=D, sC=Din, beta=1.0), dP, Xp):
+        if not side_accumulate(wk, lambda t: gemm("M", "N", D, Din, NV * L, dP, PW, Xp, Din, t, card * Din, batch=card, sA=D, sC=Din, beta=1.0), dP, Xp):
             tk = _grad_target(wk)
-            dwk = _empty((D, 2 * Din), Xp) if tk is None else None
-            gemm("M", "N", D, Din, NV * L, dP, 4 * D, Xp, Din, dwk if tk is None else tk, 2 * Din, batch=2, sA=D, sC=Din, beta=0.0 if tk is None else 1.0)
-        if not side_accumulate(wv, lambda t: gemm("M", "N", D, Din, NV * L, dP, 4 * D, Xp, Din, t, 2 * Din, batch=2, sA=D, sC=Din, A_off=2 * D,
+            dwk = _empty((D, card * Din), Xp) if tk is None else None
+            gemm("M", "N", D, Din, NV * L, dP, PW, Xp, Din, dwk if tk is None else tk, card * Din, batch=card, sA=D, sC=Din, beta=0.0 if tk is None else 1.0)
+        if not side_accumulate(wv, lambda t: gemm("M", "N", D, Din, NV * L, dP, PW, Xp, Din, t, card * Din, batch=card, sA=D, sC=Din, A_off=card * D,
                                                    beta=1.0), dP, Xp):
             tv = _grad_target(wv)
-            dwv = _empty((D, 2 * Din), Xp) if tv is None else None
-            gemm("M", "N", D, Din, NV * L, dP, 4 * D, Xp, Din, dwv if tv is None else tv, 2 * Din, batch=2, sA=D, sC=Din, A_off=2 * D,
+            dwv = _empty((D, card * Din), Xp) if tv is None else None
+            gemm("M", "N", D, Din, NV * L, dP, PW, Xp, Din, dwv if tv is None else tv, card * Din, batch=card, sA=D, sC=Din, A_off=card * D,
                  beta=0.0 if tv is None else 1.0)
-        # input grads: dXp = sum_blk dP[:, blk] @ W[:, half]
+        # input grads: dXp = sum_blk dP[:, blk] @ W[:, slot]
         dX = _empty((NV * L, Din), Xp)
         packs = None
         if TRX_PROJ_ON_CONV:
             with _x3_scope():
-                packs = _trx_wcat_packs(*getattr(ctx, "wkv", (wk, wv)))
+                packs = _trx_wcat_packs(*getattr(ctx, "wkv", (wk, wv)), card)
                 if packs is not None:      # dXp = dP @ Wcat: the data gradient of the 1x1 convolution of _trx_forward
-                    lib().call("lmkd_conv2d_bwd_data", _p(dP), _p(packs[1]), _p(dX), NV * L, 1, 1, Din, 4 * D, 1, 1, 1, 0, 0, _stream())
+                    lib().call("lmkd_conv2d_bwd_data", _p(dP), _p(packs[1]), _p(dX), NV * L, 1, 1, Din, PW, 1, 1, 1, 0, 0, _stream())
         if packs is None:
-            gemm("K", "N", NV * L, Din, D, dP, 4 * D, wk, 2 * Din, dX, Din)
-            gemm("K", "N", NV * L, Din, D, dP, 4 * D, wk, 2 * Din, dX, Din, beta=1.0, A_off=D, B_off=Din)
-            gemm("K", "N", NV * L, Din, D, dP, 4 * D, wv, 2 * Din, dX, Din, beta=1.0, A_off=2 * D)
-            gemm("K", "N", NV * L, Din, D, dP, 4 * D, wv, 2 * Din, dX, Din, beta=1.0, A_off=3 * D, B_off=Din)
+            for i, w in enumerate((wk, wv)):
+                for s_ in range(card):
+                    gemm("K", "N", NV * L, Din, D, dP, PW, w, card * Din, dX, Din, beta=0.0 if i + s_ == 0 else 1.0, A_off=(i * card + s_) * D,
+                         B_off=s_ * Din)
         if mask is not None:
             lib().call("lmkd_mul", _p(dX), _p(mask), _p(dX), dX.numel(), _stream())
         dsup = dX[:Ns * L].reshape(Ns, L, Din)
@@ -2311,7 +2393,7 @@ class TRXSupFn(torch.autograd.Function):
         logits, saved = _trx_forward(sup.contiguous(), qry.contiguous(), plan, wk, bk, wv, bv, gamma, beta, pe, mask, True)
         Xp, Kn, V, Khat, rstd, S, proto, rowmap, seg_off, seg_cnt = saved
         L, D = sup.shape[1], wk.shape[0]
-        sim, gram = _trx_sup_sim(proto, plan, qry.shape[0], L * (L - 1) // 2, D)
+        sim, gram = _trx_sup_sim(proto, plan, qry.shape[0], math.comb(L, wk.shape[1] // sup.shape[2]), D)
         ctx.save_for_backward(Xp, Kn, V, Khat, rstd, S, proto, rowmap, wk, wv, gamma, mask, gram)
         ctx.plan, ctx.seg_off, ctx.seg_cnt = plan, seg_off, seg_cnt
         ctx.shapes = (sup.shape, qry.shape)
@@ -2329,7 +2411,7 @@ def trx_sup_nograd(sup, qry, plan, wk, bk, wv, bv, gamma, beta, pe, mask=None):
     _chk(sup, qry, wk, bk, wv, bv, gamma, beta, pe, mask)
     logits, saved = _trx_forward(sup.contiguous(), qry.contiguous(), plan, wk, bk, wv, bv, gamma, beta, pe, mask, False)
     L, D = sup.shape[1], wk.shape[0]
-    return logits, _trx_sup_sim(saved[6], plan, qry.shape[0], L * (L - 1) // 2, D)[0]
+    return logits, _trx_sup_sim(saved[6], plan, qry.shape[0], math.comb(L, wk.shape[1] // sup.shape[2]), D)[0]
 
 
 def trx_logits_nograd(sup, qry, plan, wk, bk, wv, bv, gamma, beta, pe, mask=None):
