@@ -471,6 +471,28 @@ int lmkd_strm_patchdist_fwd(const float* E, const int* order, float* dist, int* 
 int lmkd_strm_patchdist_bwd(const float* E, const int* order, const int* pos, const float* dist, const int* idx, const float* g, float* dpre,
                             float* dP, int Ns, int Nq, int way, int shot, int L, int Hd, void* stream);
 
+/* ---- OTAM matcher head (teacher/code/model.py:3260-3343: cos_sim, OTAM_cum_dist, CNN_OTAM); csrc/otam.hip.
+ * fp32 tensors, fixed-order reductions, no atomics.  X [Nq * L][D] query frames, Y support frames; 1 <= L <= 16, Ns <= 512, D % 4 == 0.
+ * Every [Nq * L][.] matrix over the support frames has the row pitch ldd = Ns * L rounded up to a multiple of 4; Y, dS hold ldd rows
+ * (Y's pad rows zero).  The soft minimum is evaluated after its minimum is subtracted (finite where the reference's form underflows).
+ * Every entry point checks its shapes before it makes a HIP call. */
+/* cos_sim (:3260-3269) + `1 -` (:3333): n = X Y^T through lmkd_gemm_f32 (in its current mode), rq / rs the row norms,
+   dist = 1 - n / (rq rs + 0.01); 3 launches */
+int lmkd_otam_frame_dist_fwd(const float* X, const float* Y, float* n, float* rq, float* rs, float* dist, int Nq, int Ns, int L, int D,
+                             void* stream);
+/* OTAM_cum_dist in both directions (:3271-3299, :3338), class means and softmax (:3340-3343) in one launch, one workgroup per query:
+   cum [Nq][Ns], logits [Nq][way] (probabilities).  sup_class [Ns] on the device, sup_class_host the same on the host (checked against
+   [0, way) here).  L == 8 with Ns <= 256 keeps the table in registers, every other shape in LDS. */
+int lmkd_otam_align_fwd(const float* dist, const int* sup_class, const int* sup_class_host, float* cum, float* logits, int Nq, int Ns,
+                        int way, int L, void* stream);
+/* backward of lmkd_otam_align_fwd: the table is recomputed; dD [Nq * L][ldd], every element of the Ns * L columns written once */
+int lmkd_otam_align_bwd(const float* dlogits, const float* logits, const float* dist, const int* sup_class, const int* sup_class_host,
+                        float* dD, int Nq, int Ns, int way, int L, void* stream);
+/* backward of lmkd_otam_frame_dist_fwd: Gd [Nq * L][ldd] = -dD / den (workspace), dQ [Nq * L][D], dS [ldd][D]; one kernel for Gd and the
+   -coefficient / norm * frame terms, then two accumulating lmkd_gemm_f32 calls; 3 launches */
+int lmkd_otam_frame_dist_bwd(const float* dD, const float* X, const float* Y, const float* n, const float* rq, const float* rs, float* Gd,
+                             float* dQ, float* dS, int Nq, int Ns, int L, int D, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

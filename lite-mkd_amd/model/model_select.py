@@ -47,7 +47,11 @@ name2classifier = {
     "e_dist_fc2_sup": "e_dist_fc2_sup", "strm_res18": "strmclassifiers_resnet18",
     "strm_res18_sup": "strmclassifiers_resnet18_sup", "strm_1fc_sup": "strm_1fc_sup",
     "e_dist_1fc_sup": "e_dist_1fc_sup",
+    "otam": "OTAM",      # the ordered temporal alignment head (teacher/code/model.py:3312-3343), offered beside TRX and STRM
 }
+# classifiers that read the plain [N, seq_len, D] features, and the backbones that return a dict of two feature sets instead
+plain_feature_classifiers = ("otam",)
+two_head_backbones = ("resnet18_2fc", "resnet50_2fc", "moblienetv3_fc2")
 
 # model_select.py:220-233
 name2teacher = {
@@ -55,6 +59,7 @@ name2teacher = {
     "train_teacher": "TRX", "test_teacher": "TRX_fixed",
     "train_teacher_TRX_sup": "TRX_sup", "test_teacher_TRX_sup_fixed": "TRX_sup_fixed",
     "train_teacher_TRX_2fcsup": "TRX_2fcsup", "test_teacher_TRX_2fcsup_fixed": "TRX_2fcsup_fixed",
+    "train_teacher_otam": "OTAM", "test_teacher_otam": "OTAM_fixed",      # no parameters: no checkpoint is read
 }
 
 
@@ -79,6 +84,9 @@ def select_model_student(args):
                                   % (args.model_classifier, args.model_backbone))
     if backbone_cls is None:
         raise NotImplementedError("backbone plugin '%s' is outside the MI355X hot path (SURVEY.md 8f N1)" % args.model_backbone)
+    if args.model_classifier in plain_feature_classifiers and args.model_backbone in two_head_backbones:
+        raise NotImplementedError("classifier plugin '%s' reads plain [N, seq_len, D] features, backbone plugin '%s' returns a dict of two "
+                                  "feature sets" % (args.model_classifier, args.model_backbone))
     backbone = backbone_cls(args)
     classifier = _classifier_class(name2classifier[args.model_classifier])(args)
     # args.num_gpus > 1: the reference wraps backbone.resnet in nn.DataParallel (:205-207); here extra GPUs

@@ -2043,6 +2043,7 @@ class ClassPlan:
             order += idx
             self.counts.append(len(idx))
         self.ns = len(vals)
+        self.labels = vals                        # class of every support video, host side (OtamFn hands them to the library's checks)
         pos = [0] * self.ns                       # pos[n] = class-sorted position of support video n
         for p_, n in enumerate(order):
             pos[n] = p_
@@ -2515,6 +2516,67 @@ class EDistFn(torch.autograd.Function):
         lib().call("lmkd_mean_frames_bwd", _p(dsm), _p(dsup), Ns, L, D, _stream())
         lib().call("lmkd_mean_frames_bwd", _p(dqm), _p(dqry), Nq, L, D, _stream())
         return dsup, dqry, None
+
+
+def otam_plan_check(plan):
+    """the OTAM head's softmax runs over every class 0 .. way-1: a class without a support video (the reference returns a narrower
+    tensor there) is a ValueError, raised from the host-side plan before anything is launched"""
+    missing = [c for c in range(plan.way) if c not in plan.classes]
+    if missing:
+        raise ValueError("the OTAM head needs a support video of every class 0 .. %d: class %d has none (support classes %s)"
+                         % (plan.way - 1, missing[0], plan.classes))
+    if getattr(plan, "_labels_c", None) is None:
+        plan._labels_c = _ints(plan.labels)
+    return plan._labels_c
+
+
+def otam_pitch(Ns, L):
+    """row pitch of the [Nq * L, .] matrices over the support frames, and the row count of the support-frame matrices (include/lmkd.h)"""
+    return (Ns * L + 3) & ~3
+
+
+class OtamFn(torch.autograd.Function):
+    """CNN_OTAM.forward (teacher/code/model.py:3319-3343): frame cosine distances, the ordered alignment in both directions, class means,
+    softmax -> [Nq, way] probabilities.  No parameters.  2 library calls forward (4 launches), 2 backward (4 launches); csrc/otam.hip."""
+
+    @staticmethod
+    def forward(ctx, sup, qry, plan):
+        labels_c = otam_plan_check(plan)
+        sup, qry = sup.contiguous(), qry.contiguous()
+        _chk(sup, qry)
+        if sup.dtype != torch.float32 or qry.dtype != torch.float32 or sup.dim() != 3 or qry.shape[1:] != sup.shape[1:]:
+            raise RuntimeError("OtamFn expects fp32 [N, L, D] features; got %s %s and %s %s" % (sup.dtype, tuple(sup.shape), qry.dtype, tuple(qry.shape)))
+        Ns, L, D = sup.shape
+        Nq = qry.shape[0]
+        if plan.ns != Ns:
+            raise RuntimeError("OtamFn: %d support videos, %d support labels" % (Ns, plan.ns))
+        ldd = otam_pitch(Ns, L)
+        X, Y = qry.view(Nq * L, D), sup.view(Ns * L, D)
+        if ldd != Ns * L:      # zero pad rows: the backward's product over the support frames runs over the pitch
+            Y = torch.cat([Y, Y.new_zeros(ldd - Ns * L, D)])
+        n, dist = _empty((Nq * L, ldd), sup), _empty((Nq * L, ldd), sup)
+        rq, rs = _empty((Nq * L,), sup), _empty((Ns * L,), sup)
+        lib().call("lmkd_otam_frame_dist_fwd", _p(X), _p(Y), _p(n), _p(rq), _p(rs), _p(dist), Nq, Ns, L, D, _stream())
+        cum, logits = _empty((Nq, Ns), sup), _empty((Nq, plan.way), sup)
+        lib().call("lmkd_otam_align_fwd", _p(dist), _p(plan.cls), labels_c, _p(cum), _p(logits), Nq, Ns, plan.way, L, _stream())
+        ctx.save_for_backward(X, Y, n, rq, rs, dist, cum, logits)
+        ctx.plan, ctx.dims = plan, (Ns, Nq, L, D)
+        ctx.mark_non_differentiable(cum)
+        return logits, cum
+
+    @staticmethod
+    def backward(ctx, g, _gcum):
+        _audit.engine_owned(g)
+        X, Y, n, rq, rs, dist, cum, logits = ctx.saved_tensors
+        plan = ctx.plan
+        Ns, Nq, L, D = ctx.dims
+        ldd = otam_pitch(Ns, L)
+        dD = _empty((Nq * L, ldd), X)
+        lib().call("lmkd_otam_align_bwd", _p(g.contiguous()), _p(logits), _p(dist), _p(plan.cls), plan._labels_c, _p(dD), Nq, Ns, plan.way, L,
+                   _stream())
+        Gd, dQ, dS = _empty((Nq * L, ldd), X), _empty((Nq * L, D), X), _empty((ldd, D), X)
+        lib().call("lmkd_otam_frame_dist_bwd", _p(dD), _p(X), _p(Y), _p(n), _p(rq), _p(rs), _p(Gd), _p(dQ), _p(dS), Nq, Ns, L, D, _stream())
+        return dS[:Ns * L].view(Ns, L, D), dQ.view(Nq, L, D), None
 
 
 # ------------------------------------------------------------------------------------------
