@@ -493,6 +493,28 @@ int lmkd_otam_align_bwd(const float* dlogits, const float* logits, const float* 
 int lmkd_otam_frame_dist_bwd(const float* dD, const float* X, const float* Y, const float* n, const float* rq, const float* rs, float* Gd,
                              float* dQ, float* dS, int Nq, int Ns, int L, int D, void* stream);
 
+/* ---- CTX matcher head (teacher/code/model.py:2840-2936 CrossTransformer, the head of CTXBranch / TwoCTXShuffleTime); csrc/ctx.hip.
+ * fp32 tensors, fixed-order reductions, no atomics: two calls on the same inputs are bit-identical.  K [(Ns + Nq) * L][D] the normalised
+ * key rows, V the raw value rows, the Ns support videos first.  The classes with support are nseg <= 16 (LMKD_MAX_SEG) segments of the
+ * class-sorted support positions: order [Ns] (device) = support video at each position, seg_off / seg_cnt / seg_col (host) = first
+ * position, videos and logit column of each segment; the segments follow one another from position 0 and hold Ns videos.
+ * 1 <= L <= 16, D % 4 == 0, seg_col in [0, way), and at most 256 support FRAMES per class (seg_cnt * L <= 256: 32 shots of 8 frames; the
+ * LDS plan of the backward's first kernel).  Every entry point checks its shapes before it makes a HIP call. */
+/* nn.LayerNorm over rows (:2878-2879) that keeps Khat = (x - mean) * rstd and rstd (nullable) for lmkd_layernorm_bwd_rows; Kn may be Kraw */
+int lmkd_ctx_ln_fwd(const float* Kraw, const float* gamma, const float* beta, float* Kn, float* Khat, float* rstd, long rows, int D,
+                    float eps, void* stream);
+/* :2892-2920 for every (query, class) in ONE launch: A [Nq * L][Ns * L] (nullable; column = position * L + frame) = the softmax over the
+   class's frames of Kq Kc^T / sqrt(D), evaluated after the row maximum is subtracted; logits [Nq][way] = -|Vq - A Vc|^2 / L, 0 in the
+   columns of classes without support (written by the kernel).  The prototypes A Vc are never stored. */
+int lmkd_ctx_attend_fwd(const float* K, const float* V, const int* order, float* A, float* logits, int Ns, int Nq, int way, int L, int D,
+                        int nseg, const int* seg_off, const int* seg_cnt, const int* seg_col, void* stream);
+/* backward in TWO launches.  First, per (query, class): E [nseg][Nq * L][D] = d loss / d (Vq - A Vc) and dS [Nq * L][Ns * L] (laid out
+   like A) = d loss / d score - two workspaces, every element written.  Then dK / dV [(Ns + Nq) * L][D], every row written once: a
+   support row sums over the queries, a query row over the segments, in four interleaved partial sums added in a fixed order */
+int lmkd_ctx_attend_bwd(const float* dlogits, const float* K, const float* V, const int* order, const float* A, float* dS, float* E,
+                        float* dK, float* dV, int Ns, int Nq, int way, int L, int D, int nseg, const int* seg_off, const int* seg_cnt,
+                        const int* seg_col, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,7 +13,7 @@ import torch
 
 from . import trainloop as TL
 from .model import classifiers
-from .model.model_select import load_student, load_teacher
+from .model.model_select import load_student, load_teacher, load_teacher_ctx
 from .options import default_args
 from .utils import aggregate_accuracy
 
@@ -21,9 +21,14 @@ from .utils import aggregate_accuracy
 def select_test(args):
     """model_select.py:244-260.  'teacher': TRX_fixed with the `bracnch.transformers.<i>.*` weights of an MFM checkpoint, one entry
     per cardinality of args.temp_set (load_teacher); 'student': the checkpoint written by the training loop (load_student; commented out in the reference's
-    dict although test.py:103-104 evaluates it)."""
+    dict although test.py:103-104 evaluates it).  With --model_teacher test_teacher_ctx 'teacher' is CTX_fixed with the
+    `bracnch.transformers.*` weights of a TwoCTXShuffleTime checkpoint (load_teacher_ctx)."""
+    def teacher():
+        if getattr(args, "model_teacher", None) == "test_teacher_ctx":
+            return load_teacher_ctx(classifiers.CTX_fixed(args), args)
+        return load_teacher(classifiers.TRX_fixed(args), args)
     name2test = {
-        "teacher": lambda: load_teacher(classifiers.TRX_fixed(args), args),
+        "teacher": teacher,
         "student": lambda: load_student(args),
     }
     return name2test[args.test_model]()
@@ -76,7 +81,8 @@ def main(argv=None):
     import argparse
     ap = argparse.ArgumentParser()
     base = default_args()
-    for k in ("test_model", "test_model_path", "teacher_checkpoint", "model_backbone", "model_classifier", "distill_name", "dataset", "mode"):
+    for k in ("test_model", "test_model_path", "teacher_checkpoint", "model_backbone", "model_classifier", "model_teacher", "distill_name", "dataset",
+              "mode"):
         ap.add_argument("--" + k, default=getattr(base, k))
     for k in ("num_test_tasks", "way", "shot", "query_per_class_test", "seq_len", "img_size"):
         ap.add_argument("--" + k, type=int, default=getattr(base, k))

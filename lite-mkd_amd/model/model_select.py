@@ -50,7 +50,7 @@ name2classifier = {
     "otam": "OTAM",      # the ordered temporal alignment head (teacher/code/model.py:3312-3343), offered beside TRX and STRM
 }
 # classifiers that read the plain [N, seq_len, D] features, and the backbones that return a dict of two feature sets instead
-plain_feature_classifiers = ("otam",)
+plain_feature_classifiers = ("otam", "CTX")
 two_head_backbones = ("resnet18_2fc", "resnet50_2fc", "moblienetv3_fc2")
 
 # model_select.py:220-233
@@ -60,6 +60,7 @@ name2teacher = {
     "train_teacher_TRX_sup": "TRX_sup", "test_teacher_TRX_sup_fixed": "TRX_sup_fixed",
     "train_teacher_TRX_2fcsup": "TRX_2fcsup", "test_teacher_TRX_2fcsup_fixed": "TRX_2fcsup_fixed",
     "train_teacher_otam": "OTAM", "test_teacher_otam": "OTAM_fixed",      # no parameters: no checkpoint is read
+    "train_teacher_ctx": "CTX", "test_teacher_ctx": "CTX_fixed",          # the frame-level head of TwoCTXShuffleTime (teacher/code/model.py:3045-3121)
 }
 
 
@@ -99,6 +100,8 @@ def select_model_teacher(args):
     classifier = _classifier_class(name2teacher[args.model_teacher])(args)
     if args.model_teacher in ["test_teacher", "test_teacher_TRX_sup_fixed"]:
         classifier = load_teacher(classifier, args)
+    elif args.model_teacher == "test_teacher_ctx":
+        classifier = load_teacher_ctx(classifier, args)
     return classifier
 
 
@@ -120,6 +123,25 @@ def load_teacher(teacher, args):
             for mod, name in ((t.k_linear, "k_linear"), (t.v_linear, "v_linear"), (t.norm_k, "norm_k"), (t.norm_v, "norm_v")):
                 mod.weight.copy_(entry(pre + name + ".weight"))
                 mod.bias.copy_(entry(pre + name + ".bias"))
+    return teacher
+
+
+def load_teacher_ctx(teacher, args):
+    """copy `bracnch.transformers.*` (no index: CTXBranch holds ONE CrossTransformer, teacher/code/model.py:3057) of a TwoCTXShuffleTime
+    checkpoint into the CTX teacher head.  A missing key raises KeyError naming it."""
+    sd = torch.load(args.teacher_checkpoint, map_location="cpu")["model_state_dict"]
+    t = teacher.transformers
+
+    def entry(key):
+        if key not in sd:
+            raise KeyError("teacher checkpoint %s has no '%s' (the CTX head of a TwoCTXShuffleTime teacher)" % (args.teacher_checkpoint, key))
+        return sd[key]
+    pre = "bracnch.transformers."
+    with torch.no_grad():
+        t.pe.pe.copy_(entry(pre + "pe.pe"))
+        for mod, name in ((t.k_linear, "k_linear"), (t.v_linear, "v_linear"), (t.norm_k, "norm_k"), (t.norm_v, "norm_v")):
+            mod.weight.copy_(entry(pre + name + ".weight"))
+            mod.bias.copy_(entry(pre + name + ".bias"))
     return teacher
 
 

@@ -2579,6 +2579,116 @@ class OtamFn(torch.autograd.Function):
         return dS[:Ns * L].view(Ns, L, D), dQ.view(Nq, L, D), None
 
 
+CTX_MAX_FRAMES = 256      # support frames of one class the CTX kernels take (include/lmkd.h)
+
+
+def _ctx_layout(plan, Ns, L):
+    """the class layout lmkd_ctx_attend_* take, cached on the plan: (nseg, seg_off, seg_cnt, seg_col) over the class-sorted support
+    positions (plan.order names the video at each position)"""
+    if plan.ns != Ns:
+        raise RuntimeError("CtxLogitsFn: %d support videos, %d support labels" % (Ns, plan.ns))
+    if max(plan.counts) * L > CTX_MAX_FRAMES:
+        raise RuntimeError("CtxLogitsFn: a class with %d support videos of %d frames: the CTX kernels take %d frames per class"
+                           % (max(plan.counts), L, CTX_MAX_FRAMES))
+    lay = getattr(plan, "_ctx_layout", None)
+    if lay is None:
+        off = [sum(plan.counts[:i]) for i in range(len(plan.counts))]
+        lay = plan._ctx_layout = (len(plan.counts), _ints(off), _ints(plan.counts), _ints(plan.classes))
+    return lay
+
+
+def _ctx_forward(sup, qry, plan, wk, bk, wv, bv, gamma, beta, pe, mask, want_grad):
+    """CrossTransformer.forward (teacher/code/model.py:2859-2924) in 5 launches whatever the episode's classes look like: position
+    encoding (+ dropout), the two projections, LayerNorm of the keys, one attend launch.  -> logits [Nq, way], saved tensors"""
+    if sup.dtype != torch.float32 or sup.dim() != 3 or qry.dim() != 3 or qry.shape[1:] != sup.shape[1:]:
+        raise RuntimeError("CtxLogitsFn expects fp32 [N, L, Din] features; got %s %s and %s" % (sup.dtype, tuple(sup.shape), tuple(qry.shape)))
+    Ns, L, Din = sup.shape
+    Nq = qry.shape[0]
+    D = wk.shape[0]
+    if wk.shape != (D, Din) or wv.shape != (D, Din) or pe.shape != (L, Din):
+        raise RuntimeError("CtxLogitsFn: k_linear %s / v_linear %s / pe %s do not take frames of %d features"
+                           % (tuple(wk.shape), tuple(wv.shape), tuple(pe.shape), Din))
+    nseg, seg_off, seg_cnt, seg_col = _ctx_layout(plan, Ns, L)
+    rows = (Ns + Nq) * L
+    X = stack_rows(sup.reshape(Ns * L, Din), qry.reshape(Nq * L, Din))
+    Xp = torch.empty_like(X)
+    lib().call("lmkd_add_pe", _p(X), _p(pe), _p(mask), _p(Xp), rows, Din, L, _stream())
+    Kn, V = _empty((rows, D), X), _empty((rows, D), X)
+    gemm("K", "K", rows, D, Din, Xp, Din, wk, Din, Kn, D, bias=bk)
+    gemm("K", "K", rows, D, Din, Xp, Din, wv, Din, V, D, bias=bv)
+    Khat = _empty((rows, D), X) if want_grad else None
+    rstd = _empty((rows,), X) if want_grad else None
+    lib().call("lmkd_ctx_ln_fwd", _p(Kn), _p(gamma), _p(beta), _p(Kn), _p(Khat), _p(rstd), rows, D, _f32(1e-5), _stream())
+    A = _empty((Nq * L, Ns * L), X) if want_grad else None
+    logits = _empty((Nq, plan.way), X)
+    lib().call("lmkd_ctx_attend_fwd", _p(Kn), _p(V), _p(plan.order), _p(A), _p(logits), Ns, Nq, plan.way, L, D, nseg, seg_off, seg_cnt, seg_col,
+               _stream())
+    return logits, (Xp, Kn, V, Khat, rstd, A)
+
+
+class CtxLogitsFn(torch.autograd.Function):
+    """CrossTransformer.forward (teacher/code/model.py:2859-2924): the frame-level cross-transformer head, csrc/ctx.hip, DESIGN.md 18.
+    Parameter gradients follow TRXLogitsFn: added into .grad by the kernels where DIRECT_PARAM_GRAD allows it, else returned."""
+
+    @staticmethod
+    def forward(ctx, sup, qry, wk, bk, wv, bv, gamma, beta, pe, mask, plan):
+        _chk(sup, qry, wk, bk, wv, bv, gamma, beta, pe, mask)
+        logits, (Xp, Kn, V, Khat, rstd, A) = _ctx_forward(sup.contiguous(), qry.contiguous(), plan, wk, bk, wv, bv, gamma, beta, pe, mask, True)
+        ctx.save_for_backward(Xp, Kn, V, Khat, rstd, A, wk, wv, gamma, mask)
+        ctx.plan = plan
+        ctx.shapes = (sup.shape, qry.shape)
+        ctx.biases = (bk, bv, beta)
+        return logits
+
+    @staticmethod
+    def backward(ctx, g):
+        _audit.engine_owned(g)
+        Xp, Kn, V, Khat, rstd, A, wk, wv, gamma, mask = ctx.saved_tensors
+        plan = ctx.plan
+        (Ns, L, Din), (Nq, _, _) = ctx.shapes
+        D = wk.shape[0]
+        rows = (Ns + Nq) * L
+        nseg, seg_off, seg_cnt, seg_col = _ctx_layout(plan, Ns, L)
+        dS, E = torch.empty_like(A), _empty((nseg * Nq * L, D), Xp)
+        dKn, dV = _empty((rows, D), Xp), _empty((rows, D), Xp)
+        lib().call("lmkd_ctx_attend_bwd", _p(g.contiguous()), _p(Kn), _p(V), _p(plan.order), _p(A), _p(dS), _p(E), _p(dKn), _p(dV), Ns, Nq, plan.way,
+                   L, D, nseg, seg_off, seg_cnt, seg_col, _stream())
+        bk_, bv_, beta_ = ctx.biases
+
+        def colsum_into(param, a, b=None):
+            t = _grad_target(param)
+            if t is None:
+                return colsum(a, b)
+            colsum(a, b, out=t, accumulate=True)
+            return None
+        dgamma = colsum_into(gamma, dKn, Khat)
+        dbeta = colsum_into(beta_, dKn)
+        lib().call("lmkd_layernorm_bwd_rows", _p(dKn), _p(Khat), _p(rstd), _p(gamma), rows, D, _stream())      # dKn -> dKraw in place
+        dbk = colsum_into(bk_, dKn)
+        dbv = colsum_into(bv_, dV)
+        grads = []
+        for w, dy in ((wk, dKn), (wv, dV)):      # dW = dy^T Xp
+            dw = None
+            if not side_accumulate(w, lambda t, dy=dy: gemm("M", "N", D, Din, rows, dy, D, Xp, Din, t, Din, beta=1.0), dy, Xp):
+                t = _grad_target(w)
+                dw = _empty((D, Din), Xp) if t is None else None
+                gemm("M", "N", D, Din, rows, dy, D, Xp, Din, dw if t is None else t, Din, beta=0.0 if t is None else 1.0)
+            grads.append(dw)
+        dX = _empty((rows, Din), Xp)
+        gemm("K", "N", rows, Din, D, dKn, D, wk, Din, dX, Din)
+        gemm("K", "N", rows, Din, D, dV, D, wv, Din, dX, Din, beta=1.0)
+        if mask is not None:
+            lib().call("lmkd_mul", _p(dX), _p(mask), _p(dX), dX.numel(), _stream())
+        return (dX[:Ns * L].reshape(Ns, L, Din), dX[Ns * L:].reshape(Nq, L, Din), grads[0], dbk, grads[1], dbv, dgamma, dbeta, None, None,
+                None)
+
+
+def ctx_logits_nograd(sup, qry, plan, wk, bk, wv, bv, gamma, beta, pe, mask=None):
+    """the frozen teacher's head: the same five launches, nothing kept"""
+    _chk(sup, qry, wk, bk, wv, bv, gamma, beta, pe, mask)
+    return _ctx_forward(sup.contiguous(), qry.contiguous(), plan, wk, bk, wv, bv, gamma, beta, pe, mask, False)[0]
+
+
 # ------------------------------------------------------------------------------------------
 # loss / accuracy
 # ------------------------------------------------------------------------------------------

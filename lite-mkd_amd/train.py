@@ -427,8 +427,10 @@ def main(argv=None):
             loader = TL.StreamedEpisodes(loader, args, dev)
     student, teacher, loader, distiller, accuracy_fn, _, optimizer, scheduler = TL.make(args, video_loader=loader, base_seed=args.seed, schedule=sched)
     if args.teacher_checkpoint:
-        from .model.model_select import load_teacher
-        load_teacher(teacher.classifier if hasattr(teacher, "classifier") else teacher, args)
+        from .model.model_select import load_teacher, load_teacher_ctx
+        # (a CTX teacher's checkpoint is a TwoCTXShuffleTime one: `bracnch.transformers.*` without an index)
+        load = load_teacher_ctx if args.model_teacher in ("train_teacher_ctx", "test_teacher_ctx") else load_teacher
+        load(teacher.classifier if hasattr(teacher, "classifier") else teacher, args)
     t0 = time.time()
 
     def log(iteration, a, b):
