@@ -378,6 +378,25 @@ int lmkd_layernorm_fwd(const float* x, const float* res, long res_rows, const fl
                        long rows, int D, float eps, void* stream);
 int lmkd_mha_small(const float* qkv, float* out, int B, int L, int D, int H, void* stream);
 
+/* ---- MFM teacher fusion, training (model.py:1143-1151 TrainablePositionalEncoding.forward, :1317-1323 / :1376-1385 the fusions'
+ * forward; nn.TransformerEncoderLayer defaults: post-norm, ReLU, dropout 0.1).  fp32, no atomics, bit-identical from call to call.
+ * lmkd_layernorm_train_fwd: lmkd_layernorm_fwd that also stores xhat [rows, D] and rstd [rows]; mask (nullable, [rows, D], values 0 or
+ *   1/(1-p): the dropout after the positional-encoding LayerNorm, :1150) multiplies y.
+ * lmkd_layernorm_train_bwd: dy read at row stride lddy (a column slice of the concatenated gradient), g = dy o mask o gamma,
+ *   dpre [rows, D] = rstd (g - mean(g) - xhat mean(g xhat)); dyc (nullable, [rows, D]) receives dy o mask, the contiguous operand of the
+ *   lmkd_colsum calls that give dgamma = colsum(dyc, xhat) and dbeta = colsum(dyc).
+ * lmkd_mha_small_train_fwd: lmkd_mha_small that also writes the probabilities P [B*H, 8, 8] before dropout (zero beyond L) and applies
+ *   mask (nullable, [B*H, L, L], 0 or 1/(1-p)) to the probabilities that multiply V.
+ * lmkd_mha_small_bwd: per (sequence, head) dV = (P o M)^T dO, dP = (dO V^T) o M, dS = P o (dP - rowsum(dP o P)) / sqrt(hd), dQ = dS K,
+ *   dK = dS^T Q, written to every element of dqkv [B*L, 3D].  L <= 8. ---- */
+int lmkd_layernorm_train_fwd(const float* x, const float* res, long res_rows, const float* gamma, const float* beta, const float* mask,
+                             float* y, long ldy, float* xhat, float* rstd, long rows, int D, float eps, void* stream);
+int lmkd_layernorm_train_bwd(const float* dy, long lddy, const float* mask, const float* xhat, const float* rstd, const float* gamma,
+                             float* dpre, float* dyc, long rows, int D, void* stream);
+int lmkd_mha_small_train_fwd(const float* qkv, const float* mask, float* out, float* P, int B, int L, int D, int H, void* stream);
+int lmkd_mha_small_bwd(const float* qkv, const float* P, const float* mask, const float* dO, float* dqkv, int B, int L, int D, int H,
+                       void* stream);
+
 /* ---- D2M loss (distillers.py:7-30, 295-337), accuracy (utils.py:116-121), optimizer (trainwandb.py:101-104,141-143) ---- */
 int lmkd_d2m_loss(const float* s_kl, const float* t_kl, const float* s_ce, const long long* labels, const float* s_sup,
                   const float* t_sup, int Rq, int C, int Rs, int Cs, float T, float w_kl, float w_sup, float w_ce, float* out4,

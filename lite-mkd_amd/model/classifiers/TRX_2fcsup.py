@@ -85,7 +85,7 @@ class TemporalCrossTransformer(nn.Module):
             logits, sim = ops.TRXSupFn.apply(support_set, queries, *a) if grad else ops.trx_sup_nograd(support_set, queries, plan, *a[:8])
             return {"logits": {"support_set": sim, "query": logits}}
         if grad:
-            logits = ops.TRXLogitsFn.apply(support_set, queries, *a)
+            logits = ops.TRXLogitsFn.apply(support_set, queries, *a, getattr(self, "gemm_k_block", 0))      # set by the MFM teacher's TrxBranch
         else:
             logits = ops.trx_logits_nograd(support_set, queries, plan, *a[:8])
         return {"logits": logits}

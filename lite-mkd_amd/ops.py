@@ -4,6 +4,7 @@ graph); all arithmetic of the hot path happens in liblmkd_hip.so.
 
 Activations are NHWC fp32.  Every wrapper checks device/dtype/contiguity and raises on misuse."""
 import ctypes
+import functools
 import os
 import itertools
 import math
@@ -96,9 +97,18 @@ def _empty_act(shape, like):
 # GEMM
 # ------------------------------------------------------------------------------------------
 def gemm(layA, layB, M, N, K, A, lda, B, ldb, C, ldc, alpha=1.0, beta=0.0, bias=None, relu=False,
-         batch=1, sA=0, sB=0, sC=0, A_off=0, B_off=0, C_off=0, split_k=None):
+         batch=1, sA=0, sB=0, sC=0, A_off=0, B_off=0, C_off=0, split_k=None, k_block=0):
     """C = alpha*op(A)*op(B) + beta*C + bias.  *_off are element offsets into the tensors' storage.
-    split_k: True / False forces lmkd_gemm_f32_splitk / lmkd_gemm_f32 for this call (None: the module default GEMM_SPLIT_K)"""
+    split_k: True / False forces lmkd_gemm_f32_splitk / lmkd_gemm_f32 for this call (None: the module default GEMM_SPLIT_K).
+    k_block (a multiple of 4, 0: off): sum K in blocks of that many terms, one launch per block, each adding its product of a fresh
+    accumulator to C in the epilogue (beta = 1; bias and ReLU with the last).  A kernel's accumulator takes its K terms one after the
+    other, so its rounding error grows like K; in blocks it grows like sqrt(K k_block), which is what a blocked CPU GEMM has."""
+    if k_block and K > k_block:
+        for k0 in range(0, K, k_block):
+            kk, last = min(k_block, K - k0), k0 + k_block >= K
+            gemm(layA, layB, M, N, kk, A, lda, B, ldb, C, ldc, alpha, beta if k0 == 0 else 1.0, bias if last else None, relu and last,
+                 batch, sA, sB, sC, A_off + (k0 if layA == "K" else k0 * lda), B_off + (k0 if layB == "K" else k0 * ldb), C_off, split_k, 0)
+        return C
     _chk(A, B, C, bias)
     es = 4
     if _audit.ON:
@@ -116,6 +126,11 @@ def gemm(layA, layB, M, N, K, A, lda, B, ldb, C, ldc, alpha=1.0, beta=0.0, bias=
                ctypes.c_void_p(B.data_ptr() + B_off * es), ldb, sB, _f32(beta),
                ctypes.c_void_p(C.data_ptr() + C_off * es), ldc, sC, _p(bias), int(relu), batch, _stream())
     return C
+
+
+def _gemm_in_blocks(k_block):
+    """gemm with this k_block where the call passes none"""
+    return functools.partial(gemm, k_block=k_block) if k_block else gemm
 
 
 # split-K workspace (32 MB) + ticket words of lmkd_gemm_f32_splitk, one pair per (device, stream): GEMMs of two streams may run together.
@@ -145,12 +160,12 @@ def stack_rows(a, b):
     return torch.cat([a, b], 0)
 
 
-def linear_fwd(x, w, b):
+def linear_fwd(x, w, b, k_block=0):
     """y[M,N] = x[M,K] w[N,K]^T + b"""
     M, K = x.shape
     N = w.shape[0]
     y = _empty((M, N), x)
-    return gemm("K", "K", M, N, K, x, K, w, K, y, N, bias=b)
+    return gemm("K", "K", M, N, K, x, K, w, K, y, N, bias=b, k_block=k_block)
 
 
 # Ticket buffers of the single-launch column reductions (lmkd_ticket_words() zeroed int32 words, left zeroed by every launch): one
@@ -166,11 +181,21 @@ def _tickets(like):
     return t
 
 
+COLSUM_MAX_COLS = 16384      # lmkd_colsum: cdiv(C, 32) ticket words of 512
+
+
 def colsum(a, b=None, out=None, accumulate=False):
+    """out[c] (+)= sum_r a[r, c] (* b[r, c]).  lmkd_colsum takes 16384 columns; a wider tensor (the 18432-wide in_proj bias gradient of the
+    MFM teacher's three-modality fusion) goes through it in column blocks, each copied to a contiguous tensor first."""
     rows, C = a.shape
     if out is None:
         out = _empty((C,), a)
         accumulate = False
+    if C > COLSUM_MAX_COLS:
+        for c0 in range(0, C, COLSUM_MAX_COLS):
+            c1 = min(C, c0 + COLSUM_MAX_COLS)
+            colsum(a[:, c0:c1].contiguous(), None if b is None else b[:, c0:c1].contiguous(), out[c0:c1], accumulate)
+        return out
     _chk(a, b, out)
     ws = torch.empty(lib().value("lmkd_colsum_workspace", C), dtype=torch.uint8, device=a.device)
     lib().call("lmkd_colsum", _p(a), _p(b), _p(out), rows, C, int(accumulate), _p(ws), _p(_tickets(a)), _stream())
@@ -262,15 +287,17 @@ def _pack_linear(w, w4, K):
 
 
 class LinearFn(torch.autograd.Function):
-    """nn.Linear (resnet18_2fc.py:56-64 fc1/fc2).  fwd/dgrad/wgrad on the MFMA GEMM, bias grad = column sum."""
+    """nn.Linear (resnet18_2fc.py:56-64 fc1/fc2).  fwd/dgrad/wgrad on the MFMA GEMM, bias grad = column sum.
+    k_block: gemm's, for the forward and the input gradient (the weight gradient sums over the rows)."""
 
     @staticmethod
-    def forward(ctx, x, w, b):
+    def forward(ctx, x, w, b, k_block=0):
         x = x.contiguous()
         ctx.save_for_backward(x, w)
         ctx.has_bias = b is not None
         ctx.bias = b
-        return linear_fwd(x, w.contiguous(), b)
+        ctx.k_block = k_block
+        return linear_fwd(x, w.contiguous(), b, k_block)
 
     @staticmethod
     def backward(ctx, dy):
@@ -282,7 +309,7 @@ class LinearFn(torch.autograd.Function):
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
             dx = _empty((M, K), x)
-            gemm("K", "N", M, K, N, dy, N, w, K, dx, K)          # dx = dy @ W
+            gemm("K", "N", M, K, N, dy, N, w, K, dx, K, k_block=ctx.k_block)          # dx = dy @ W
         if ctx.needs_input_grad[1]:
             tw = _grad_target(w)
             if side_accumulate(w, lambda t: gemm("M", "N", N, K, M, dy, N, x, K, t, K, beta=1.0), dy, x):
@@ -298,7 +325,7 @@ class LinearFn(torch.autograd.Function):
                 colsum(dy, out=tb, accumulate=True)
             else:
                 db = colsum(dy)
-        return dx, dw, db
+        return dx, dw, db, None
 
 
 # fc1 / fc2 over the support-frame and the query-frame features (resnet18_2fc.py:56-64: four nn.Linear calls on 200-row inputs) as ONE
@@ -2199,9 +2226,10 @@ def _trx_class_slots(counts, T):
     return out
 
 
-def _trx_forward(sup, qry, plan, wk, bk, wv, bv, gamma, beta, pe, mask, want_grad):
+def _trx_forward(sup, qry, plan, wk, bk, wv, bv, gamma, beta, pe, mask, want_grad, k_block=0):
     """Shared by the student heads (with grad) and the frozen teacher head.
-    sup [Ns,L,2048], qry [Nq,L,2048] -> logits [Nq,way] (+ saved tensors)"""
+    sup [Ns,L,2048], qry [Nq,L,2048] -> logits [Nq,way] (+ saved tensors).  k_block: gemm's, for every GEMM of the head (the MFM teacher's)"""
+    gemm = _gemm_in_blocks(k_block)
     Ns, L, Din = sup.shape
     Nq = qry.shape[0]
     D = wk.shape[0]
@@ -2264,25 +2292,27 @@ class TRXLogitsFn(torch.autograd.Function):
     """TemporalCrossTransformer.forward (TRX_2fcsup.py:74-148) for one head."""
 
     @staticmethod
-    def forward(ctx, sup, qry, wk, bk, wv, bv, gamma, beta, pe, mask, plan):
+    def forward(ctx, sup, qry, wk, bk, wv, bv, gamma, beta, pe, mask, plan, k_block=0):
         _chk(sup, qry, wk, bk, wv, bv, gamma, beta, pe, mask)
-        logits, saved = _trx_forward(sup.contiguous(), qry.contiguous(), plan, wk, bk, wv, bv, gamma, beta, pe, mask, True)
+        logits, saved = _trx_forward(sup.contiguous(), qry.contiguous(), plan, wk, bk, wv, bv, gamma, beta, pe, mask, True, k_block)
         Xp, Kn, V, Khat, rstd, S, proto, rowmap, seg_off, seg_cnt = saved
         ctx.save_for_backward(Xp, Kn, V, Khat, rstd, S, proto, rowmap, wk, wv, gamma, mask)
         ctx.plan, ctx.seg_off, ctx.seg_cnt = plan, seg_off, seg_cnt
         ctx.shapes = (sup.shape, qry.shape)
         ctx.biases = (bk, bv, beta)
         ctx.wkv = (wk, wv)      # the parameter OBJECTS (saved tensors come back as other Python objects): identity keys of the caches
+        ctx.k_block = k_block
         return logits
 
     @staticmethod
     def backward(ctx, g):
         _audit.engine_owned(g)
-        return _trx_backward(ctx, g)
+        return _trx_backward(ctx, g) + (None,)
 
 
 def _trx_backward(ctx, g, gsim=None, gram=None):
         """backward of TRXLogitsFn (g: d logits) and TRXSupFn (+ gsim: d of the prototype cosine similarities)"""
+        gemm = _gemm_in_blocks(getattr(ctx, "k_block", 0))
         Xp, Kn, V, Khat, rstd, S, proto, rowmap, wk, wv, gamma, mask = ctx.saved_tensors[:12]
         plan, seg_off, seg_cnt = ctx.plan, ctx.seg_off, ctx.seg_cnt
         (Ns, L, Din), (Nq, _, _) = ctx.shapes
@@ -3194,7 +3224,7 @@ class LinearXFn(torch.autograd.Function):
     seg: rows [0, seg) come from the support frames, the rest from the query frames (_row_segments)."""
 
     @staticmethod
-    def forward(ctx, x, w, b, relu, res, seg=0):
+    def forward(ctx, x, w, b, relu, res, seg=0, k_block=0):
         x = x.contiguous()
         w = w.contiguous()
         _strm_chk(x, w, b, res)
@@ -3204,11 +3234,12 @@ class LinearXFn(torch.autograd.Function):
         N = w.shape[0]
         y = res.contiguous().clone() if res is not None else _empty((M, N), x)
         for r0, rows in _row_segments(M, seg):
-            gemm("K", "K", rows, N, K, x, K, w, K, y, N, beta=1.0 if res is not None else 0.0, bias=b, relu=relu, A_off=r0 * K, C_off=r0 * N)
+            gemm("K", "K", rows, N, K, x, K, w, K, y, N, beta=1.0 if res is not None else 0.0, bias=b, relu=relu, A_off=r0 * K, C_off=r0 * N,
+                 k_block=k_block)
         if relu and STRM_TAPS is not None:
             STRM_TAPS.setdefault("relu", []).append(y > 0)
         ctx.save_for_backward(x, w, y if relu else None)
-        ctx.has_res, ctx.seg = res is not None, seg
+        ctx.has_res, ctx.seg, ctx.k_block = res is not None, seg, k_block
         return y
 
     @staticmethod
@@ -3226,13 +3257,13 @@ class LinearXFn(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             dx = _empty((M, K), x)
             for r0, rows in _row_segments(M, ctx.seg):
-                gemm("K", "N", rows, K, N, g, N, w, K, dx, K, A_off=r0 * N, C_off=r0 * K)
+                gemm("K", "N", rows, K, N, g, N, w, K, dx, K, A_off=r0 * N, C_off=r0 * K, k_block=ctx.k_block)
         if ctx.needs_input_grad[1]:
             dw = _empty((N, K), x)
             gemm("M", "N", N, K, M, g, N, x, K, dw, K)
         if ctx.needs_input_grad[2]:
             db = colsum(g)
-        return dx, dw, db, None, (dy if ctx.has_res else None), None
+        return dx, dw, db, None, (dy if ctx.has_res else None), None, None
 
 
 class PatchMeanFn(torch.autograd.Function):
@@ -3397,3 +3428,199 @@ def strm_patchdist_grads(Xd, w, E, plan, dist, idx, g, mask, Ns, Nq, L):
     if mask is not None:
         lib().call("lmkd_mul", _p(dX), _p(mask), _p(dX), dX.numel(), _stream())
     return dX, dw, db
+
+
+# ------------------------------------------------------------------------------------------
+# MFM teacher fusion, training (teacher/mfm.py; csrc/mfm.hip): the parts of nn.TransformerEncoderLayer that are not GEMMs,
+# as autograd Functions on the current stream.  Parameter gradients go back through autograd: the direct-accumulation paths above
+# belong to the student's pipelined episode, and the teacher trainer owns a plain optimizer step.
+# ------------------------------------------------------------------------------------------
+MFM_LN_EPS = 1e-5
+
+
+class MaskMulFn(torch.autograd.Function):
+    """x o mask: a feature dropout (nn.Dropout) whose mask (0 or 1/(1-p), lmkd_dropout_mask) the caller made"""
+
+    @staticmethod
+    def forward(ctx, x, mask):
+        x = x.contiguous()
+        _chk(x, mask)
+        if mask.shape != x.shape:
+            raise RuntimeError("dropout mask %s for a %s tensor" % (tuple(mask.shape), tuple(x.shape)))
+        ctx.save_for_backward(mask)
+        y = torch.empty_like(x)
+        lib().call("lmkd_mul", _p(x), _p(mask), _p(y), x.numel(), _stream())
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        _audit.engine_owned(dy)
+        mask, = ctx.saved_tensors
+        dy = dy.contiguous()
+        dx = torch.empty_like(dy)
+        lib().call("lmkd_mul", _p(dy), _p(mask), _p(dx), dy.numel(), _stream())
+        return dx, None
+
+
+def feature_dropout(x, mask):
+    return x if mask is None else MaskMulFn.apply(x, mask)
+
+
+class SumFn(torch.autograd.Function):
+    """x_0 + x_1 + ... in that order on lmkd_axpby (the three fused features, model.py:1632-1633)"""
+
+    @staticmethod
+    def forward(ctx, *xs):
+        xs = [x.contiguous() for x in xs]
+        _chk(*xs)
+        if any(x.shape != xs[0].shape for x in xs):
+            raise RuntimeError("SumFn: shapes %s" % [tuple(x.shape) for x in xs])
+        out = torch.empty_like(xs[0])
+        for i, x in enumerate(xs):
+            lib().call("lmkd_axpby", _p(x), _p(out), _f32(1.0), _f32(1.0 if i else 0.0), out.numel(), _stream())
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        _audit.engine_owned(g)
+        return tuple(g if need else None for need in ctx.needs_input_grad)
+
+
+class MfmLayerNormFn(torch.autograd.Function):
+    """LayerNorm(x + res) * gamma + beta, the post-norm of nn.TransformerEncoderLayer (norm1 / norm2): x, res [rows, D].
+    Saved for the backward: xhat [rows, D], rstd [rows]."""
+
+    @staticmethod
+    def forward(ctx, x, res, gamma, beta):
+        x, res = x.contiguous(), res.contiguous()
+        _chk(x, res, gamma, beta)
+        rows, D = x.shape
+        y, xhat, rstd = _empty((rows, D), x), _empty((rows, D), x), _empty((rows,), x)
+        lib().call("lmkd_layernorm_train_fwd", _p(x), _p(res), rows, _p(gamma), _p(beta), None, _p(y), D, _p(xhat), _p(rstd), rows, D,
+                   _f32(MFM_LN_EPS), _stream())
+        ctx.save_for_backward(xhat, rstd, gamma)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        _audit.engine_owned(dy)
+        xhat, rstd, gamma = ctx.saved_tensors
+        dy = dy.contiguous()
+        rows, D = xhat.shape
+        dpre = _empty((rows, D), dy)
+        lib().call("lmkd_layernorm_train_bwd", _p(dy), D, None, _p(xhat), _p(rstd), _p(gamma), _p(dpre), None, rows, D, _stream())
+        dgamma = colsum(dy, xhat) if ctx.needs_input_grad[2] else None
+        dbeta = colsum(dy) if ctx.needs_input_grad[3] else None
+        return dpre, dpre, dgamma, dbeta      # d(x + res) reaches both summands
+
+
+class MfmPosCatFn(torch.autograd.Function):
+    """cat_i( dropout_i( LayerNorm_i(x_i + emb_i[r mod L]) ) ) -> [rows, n * d]  (TrainablePositionalEncoding.forward, model.py:1143-1151,
+    and the torch.cat of the fusions' forward, :1321 / :1381).  Arguments after L: per modality x [rows, d], emb [L, d], gamma, beta,
+    mask ([rows, d] or None).  Each LayerNorm writes its column slice of the result; in the backward each reads its slice of the
+    gradient at the result's row stride.  The embedding gradient is the sum of dpre over the videos per position."""
+
+    @staticmethod
+    def forward(ctx, L, *a):
+        n = len(a) // 5
+        if len(a) != 5 * n or n == 0:
+            raise RuntimeError("MfmPosCatFn: five arguments per modality")
+        xs = [a[5 * i].contiguous() for i in range(n)]
+        embs = [a[5 * i + 1].contiguous() for i in range(n)]
+        rows, d = xs[0].shape
+        D = n * d
+        for i in range(n):
+            _chk(xs[i], embs[i], a[5 * i + 2], a[5 * i + 3], a[5 * i + 4])
+            if xs[i].shape != (rows, d) or embs[i].shape != (L, d) or rows % L:
+                raise RuntimeError("MfmPosCatFn: modality %d is %s with embeddings %s, expected (%d, %d) and (%d, %d)"
+                                   % (i, tuple(xs[i].shape), tuple(embs[i].shape), rows, d, L, d))
+            if a[5 * i + 4] is not None and a[5 * i + 4].shape != (rows, d):
+                raise RuntimeError("MfmPosCatFn: dropout mask %s for rows of %s" % (tuple(a[5 * i + 4].shape), (rows, d)))
+        cat = _empty((rows, D), xs[0])
+        saved = []
+        for i in range(n):
+            gamma, beta, mask = a[5 * i + 2], a[5 * i + 3], a[5 * i + 4]
+            xhat, rstd = _empty((rows, d), cat), _empty((rows,), cat)
+            if _audit.ON:
+                _audit.note(cat)
+            lib().call("lmkd_layernorm_train_fwd", _p(xs[i]), _p(embs[i]), L, _p(gamma), _p(beta), _p(mask),
+                       ctypes.c_void_p(cat.data_ptr() + 4 * i * d), D, _p(xhat), _p(rstd), rows, d, _f32(MFM_LN_EPS), _stream())
+            saved += [xhat, rstd, gamma, mask]
+        ctx.save_for_backward(*saved)
+        ctx.n, ctx.L = n, L
+        return cat
+
+    @staticmethod
+    def backward(ctx, dcat):
+        _audit.engine_owned(dcat)
+        dcat = dcat.contiguous()
+        n, L = ctx.n, ctx.L
+        rows, D = dcat.shape
+        d = D // n
+        out = [None]
+        for i in range(n):
+            xhat, rstd, gamma, mask = ctx.saved_tensors[4 * i:4 * i + 4]
+            need = ctx.needs_input_grad[1 + 5 * i:1 + 5 * i + 4]
+            dpre = _empty((rows, d), dcat)
+            dyc = _empty((rows, d), dcat) if need[2] or need[3] else None
+            if _audit.ON:
+                _audit.note(dcat)
+            lib().call("lmkd_layernorm_train_bwd", ctypes.c_void_p(dcat.data_ptr() + 4 * i * d), D, _p(mask), _p(xhat), _p(rstd), _p(gamma),
+                       _p(dpre), _p(dyc), rows, d, _stream())
+            demb = colsum(dpre.view(rows // L, L * d)).view(L, d) if need[1] else None
+            out += [dpre if need[0] else None, demb, colsum(dyc, xhat) if need[2] else None, colsum(dyc) if need[3] else None, None]
+        return tuple(out)
+
+
+class MfmAttnFn(torch.autograd.Function):
+    """self-attention over L <= 8 tokens per (sequence, head): qkv [B*L, 3D] -> [B*L, D]; mask [B*H, L, L] (or None) is the dropout on the
+    probabilities.  Saved for the backward: qkv, the probabilities before dropout [B*H, 8, 8], the mask."""
+
+    @staticmethod
+    def forward(ctx, qkv, mask, L, H):
+        qkv = qkv.contiguous()
+        _chk(qkv, mask)
+        M, D3 = qkv.shape
+        D = D3 // 3
+        if D3 != 3 * D or M % L:
+            raise RuntimeError("MfmAttnFn: qkv %s for sequences of %d tokens" % (tuple(qkv.shape), L))
+        B = M // L
+        if mask is not None and mask.shape != (B * H, L, L):
+            raise RuntimeError("MfmAttnFn: mask %s, expected %s" % (tuple(mask.shape), (B * H, L, L)))
+        out, P = _empty((M, D), qkv), _empty((B * H, 8, 8), qkv)
+        lib().call("lmkd_mha_small_train_fwd", _p(qkv), _p(mask), _p(out), _p(P), B, L, D, H, _stream())
+        ctx.save_for_backward(qkv, P, mask)
+        ctx.dims = (B, L, D, H)
+        return out
+
+    @staticmethod
+    def backward(ctx, dO):
+        _audit.engine_owned(dO)
+        qkv, P, mask = ctx.saved_tensors
+        dO = dO.contiguous()
+        B, L, D, H = ctx.dims
+        dqkv = torch.empty_like(qkv)
+        lib().call("lmkd_mha_small_bwd", _p(qkv), _p(P), _p(mask), _p(dO), _p(dqkv), B, L, D, H, _stream())
+        return dqkv, None, None, None
+
+
+MFM_LAYER_SITES = ("attn", "dropout1", "dropout", "dropout2")
+# The fusions' Linear layers sum 2048 - 18432 terms per output; they are summed in blocks of this many (gemm's k_block), which keeps the
+# rounding of the whole teacher's gradients at the level of a blocked CPU GEMM (DESIGN.md 19).  At widths up to it nothing changes.
+MFM_K_BLOCK = 128
+
+
+def mfm_encoder_layer_train(x, layer, L, nhead, masks=None):
+    """one nn.TransformerEncoderLayer (defaults: post-norm, ReLU, eps 1e-5, batch_first) with autograd.  x [B*L, D]; masks: None (no
+    dropout) or a dict over MFM_LAYER_SITES - "attn" [B*H, L, L] on the attention probabilities, "dropout1" [B*L, D] on the out_proj
+    output, "dropout" [B*L, dim_feedforward] after the ReLU, "dropout2" [B*L, D] on the linear2 output; a missing site has none."""
+    m = masks or {}
+    at = layer.self_attn
+    kb = MFM_K_BLOCK
+    qkv = LinearFn.apply(x, at.in_proj_weight, at.in_proj_bias, kb)
+    a = MfmAttnFn.apply(qkv, m.get("attn"), L, nhead)
+    o = feature_dropout(LinearFn.apply(a, at.out_proj.weight, at.out_proj.bias, kb), m.get("dropout1"))
+    x = MfmLayerNormFn.apply(x, o, layer.norm1.weight, layer.norm1.bias)
+    h = feature_dropout(LinearXFn.apply(x, layer.linear1.weight, layer.linear1.bias, True, None, 0, kb), m.get("dropout"))
+    f = feature_dropout(LinearFn.apply(h, layer.linear2.weight, layer.linear2.bias, kb), m.get("dropout2"))
+    return MfmLayerNormFn.apply(x, f, layer.norm2.weight, layer.norm2.bias)

@@ -3,6 +3,10 @@ TrainablePositionalEncoding :1135-1151, ThreeTransforTemproal :1300-1331, TwoTra
 ThreeTRXShiftLoopTime.extract_feature :1648-1664).  Inference (eval mode, no grad), which is how the student path
 consumes it: rgb / depth / flow ResNet-50 features [N,8,2048] -> fused teacher feature [N,8,2048].
 
+Training (the fusions' `forward`, :1317-1323 / :1376-1385, and ThreeTRXShiftLoopTime.forward :1597-1636): `_Fusion.forward` runs the same
+arithmetic with autograd - LayerNorm and attention on the training kernels of csrc/mfm.hip through ops.MfmPosCatFn / MfmAttnFn /
+MfmLayerNormFn, the five Linear layers on ops.LinearFn / LinearXFn - and the reference's dropouts as explicit masks.
+
 Parameters live in the same torch containers as the reference (nn.Embedding, nn.LayerNorm,
 nn.TransformerEncoder(nn.TransformerEncoderLayer(d_model, nhead, batch_first=True)), nn.Linear) so the state_dict keys
 (`three_fusion.transformer_encoder.layers.0.self_attn.in_proj_weight`, `fusion.f1.weight`, ...) match the reference's
@@ -77,6 +81,54 @@ class _Fusion(nn.Module):
         self.f1 = nn.Linear(in_channels * n_mod, in_channels)
         self.dropout = nn.Dropout(dropout)
 
+    def dropout_shapes(self, N, L):
+        """{site: (shape, p)} of every dropout of one forward over N videos of L tokens, in the order their seeds are drawn:
+        "pe<i>" after each positional-encoding LayerNorm (model.py:1150), per layer "l<k>.attn" on the attention probabilities,
+        "l<k>.dropout1" on the out_proj output, "l<k>.dropout" after the ReLU, "l<k>.dropout2" on the linear2 output (nn.TransformerEncoderLayer),
+        "f1" after f1 (:1323 / :1385)"""
+        d, D = self.in_channels, self.in_channels * self.n_mod
+        sites = {}
+        for i in range(self.n_mod):
+            sites["pe%d" % (i + 1)] = ((N * L, d), getattr(self, "positionEncoding%d" % (i + 1)).dropout.p)
+        for k, layer in enumerate(self.transformer_encoder.layers):
+            sites["l%d.attn" % k] = ((N * self.n_mod, L, L), float(layer.self_attn.dropout))
+            sites["l%d.dropout1" % k] = ((N * L, D), layer.dropout1.p)
+            sites["l%d.dropout" % k] = ((N * L, layer.linear1.out_features), layer.dropout.p)
+            sites["l%d.dropout2" % k] = ((N * L, D), layer.dropout2.p)
+        sites["f1"] = ((N * L, d), self.dropout.p)
+        return sites
+
+    def draw_masks(self, N, L, device):
+        """one seed per site and call from torch's default generator, as TemporalCrossTransformer.draw_dropout_seed() draws them"""
+        from ..model.classifiers.TRX_2fcsup import TemporalCrossTransformer
+        return {site: ops.dropout_mask(shape, p, TemporalCrossTransformer.draw_dropout_seed(), device)
+                for site, (shape, p) in self.dropout_shapes(N, L).items() if p > 0.0}
+
+    def forward(self, *mods, masks=None):
+        """mods: n_mod tensors [N, L, d] -> fused [N, L, d], with autograd.  masks: {site: mask} over dropout_shapes() (values 0 or
+        1/(1-p); a missing site has no dropout); None: in training mode the masks are drawn, in eval mode there is no dropout."""
+        if len(mods) != self.n_mod:
+            raise ValueError("%d modalities for a fusion of %d" % (len(mods), self.n_mod))
+        N, L, d = mods[0].shape
+        if d != self.in_channels or L > 8:
+            raise ValueError("features %s: the fusion takes [N, L <= 8, %d]" % (tuple(mods[0].shape), self.in_channels))
+        if masks is None:
+            masks = self.draw_masks(N, L, mods[0].device) if self.training else {}
+        else:
+            unknown = set(masks) - set(self.dropout_shapes(N, L))
+            if unknown:
+                raise KeyError("no dropout site %s" % sorted(unknown))
+        a = []
+        for i, m in enumerate(mods):
+            pe = getattr(self, "positionEncoding%d" % (i + 1))
+            a += [m.reshape(N * L, d), pe.position_embeddings.weight[:L], pe.LayerNorm.weight, pe.LayerNorm.bias, masks.get("pe%d" % (i + 1))]
+        h = ops.MfmPosCatFn.apply(L, *a)
+        for k, layer in enumerate(self.transformer_encoder.layers):
+            pre = "l%d." % k
+            h = ops.mfm_encoder_layer_train(h, layer, L, self.n_mod, {s: masks.get(pre + s) for s in ops.MFM_LAYER_SITES})
+        out = ops.feature_dropout(ops.LinearFn.apply(h, self.f1.weight, self.f1.bias, ops.MFM_K_BLOCK), masks.get("f1"))
+        return out.reshape(N, L, d)
+
     @torch.no_grad()
     def extract_feature(self, *mods):
         if self.training:
@@ -106,15 +158,52 @@ class TwoTransforFusion(_Fusion):
         super().__init__(args, 2, in_channels, dropout)
 
 
-class ThreeTRXShiftLoopTime(nn.Module):
-    """model.py:1588-1664, the parts the student path uses: `three_fusion`, `fusion`, `extract_feature`.
-    (`bracnch`, the teacher's own TRX head, is the TRX_2fcsup_fixed classifier of model_select.)"""
+class TrxBranch(nn.Module):
+    """model.py:1094-1128: one TemporalCrossTransformer per entry of args.temp_set, logits averaged"""
 
-    def __init__(self, args, in_channels=2048):
+    def __init__(self, args):
+        super().__init__()
+        from ..model.classifiers.TRX_2fcsup import TemporalCrossTransformer, temp_set_of
+        self.transformers = nn.ModuleList([TemporalCrossTransformer(args, s) for s in temp_set_of(args)])
+
+    def forward(self, context_features, target_features, context_labels):
+        from ..model.classifiers.TRX_2fcsup import head_logits
+        for t in self.transformers:      # the head's 2048- and 1152-term sums in blocks, like the fusions' (DESIGN.md 19)
+            t.gemm_k_block = ops.MFM_K_BLOCK
+        return {"logits": head_logits(self.transformers, context_features, context_labels, target_features)}
+
+
+class ThreeTRXShiftLoopTime(nn.Module):
+    """model.py:1588-1664.  The student path uses `three_fusion`, `fusion` and `extract_feature` (there `bracnch`, the teacher's own
+    TRX head, is the TRX_2fcsup_fixed classifier of model_select).  head=True adds `bracnch` (keys `bracnch.transformers.<i>.*`) and with
+    it `forward`, the teacher's training forward."""
+
+    def __init__(self, args, in_channels=2048, head=False):
         super().__init__()
         self.args = args
+        if head:
+            if in_channels != 2048:
+                raise ValueError("head=True: the TRX head reads features of width 2048, not in_channels = %d" % in_channels)
+            self.bracnch = TrxBranch(args)
         self.fusion = TwoTransforFusion(args, in_channels=in_channels)
         self.three_fusion = ThreeTransforTemproal(args, in_channels=in_channels)
+
+    def forward(self, context_features, context_labels, target_features):
+        """model.py:1597-1636: dicts keyed by args.m1 / m2 / m3 -> {"logits": [Nq, way]}.  As there, the second modality is rolled by
+        shirt_num for its fusion with the first, and the third is not: cat(x[:, :s], x[:, s:]) (:1613-1619) is x itself.  Every
+        operation of the fusions is per video, so support and query videos share one call per fusion use; the shared `fusion`
+        module is used twice and autograd sums its gradients."""
+        if not hasattr(self, "bracnch"):
+            raise RuntimeError("ThreeTRXShiftLoopTime.forward needs the TRX head: construct with head=True")
+        a = self.args
+        L, d, s = a.seq_len, self.three_fusion.in_channels, a.shirt_num
+        c = [context_features[m].reshape(-1, L, d) for m in (a.m1, a.m2, a.m3)]
+        t = [target_features[m].reshape(-1, L, d) for m in (a.m1, a.m2, a.m3)]
+        ns = c[0].shape[0]
+        first, second, third = (torch.cat((ci, ti), dim=0) for ci, ti in zip(c, t))
+        second_shuffle = torch.cat((second[:, s:], second[:, :s]), dim=1)
+        fused = ops.SumFn.apply(self.three_fusion(first, second, third), self.fusion(first, second_shuffle), self.fusion(first, third))
+        return self.bracnch(fused[:ns], fused[ns:], context_labels)
 
     @torch.no_grad()
     def extract_feature(self, feature):
