@@ -7,7 +7,7 @@
 // The prototypes A Vc are never stored: forward and backward form them column by column in registers; the backward keeps
 // E = d loss / d (Vq - A Vc) between its two launches.  A (and the backward's dS) are [Nq L][Ns L] with column p L + frame.  Every sum
 // runs in a fixed order: no atomics, two calls are bit-identical.
-#include "common.h"
+#include "rows.h"
 #include <atomic>
 
 #define LMKD_MAX_SEG 16
@@ -28,33 +28,14 @@ struct CxSegs {
   int col[LMKD_MAX_SEG];   // logit column (the class label)
 };
 
-// LayerNorm over the rows of Kraw that keeps what lmkd_layernorm_bwd_rows reads; Kn may be Kraw itself
-__global__ __launch_bounds__(CX_THREADS) void ctx_ln_fwd_kernel(const float* Kraw, const float* __restrict__ gamma,
-                                                                const float* __restrict__ beta, float* Kn, float* __restrict__ Khat,
-                                                                float* __restrict__ rstd_out, int D, float eps) {
-  __shared__ float red[4];
-  const long r = blockIdx.x;
-  const float* x = Kraw + r * D;
-  float s = 0.f;
-  for (int d = threadIdx.x; d < D; d += CX_THREADS) s += x[d];
-  const float mean = block_sum_256(s, red) / (float)D;
-  float q = 0.f;
-  for (int d = threadIdx.x; d < D; d += CX_THREADS) { const float c = x[d] - mean; q += c * c; }
-  const float rstd = 1.f / sqrtf(block_sum_256(q, red) / (float)D + eps);
-  for (int d = threadIdx.x; d < D; d += CX_THREADS) {
-    const float h = (x[d] - mean) * rstd;
-    if (Khat) Khat[r * D + d] = h;
-    Kn[r * D + d] = h * gamma[d] + beta[d];
-  }
-  if (threadIdx.x == 0 && rstd_out) rstd_out[r] = rstd;
-}
-
+// LayerNorm over the rows of Kraw that keeps what lmkd_layernorm_bwd_rows reads (Khat and rstd, nullable); Kn may be Kraw itself.  The
+// instance of csrc/rows.h that re-reads the row from global memory: no LDS limit on D
 extern "C" int lmkd_ctx_ln_fwd(const float* Kraw, const float* gamma, const float* beta, float* Kn, float* Khat, float* rstd, long rows,
                                int D, float eps, void* stream) {
   LMKD_REQUIRE(rows >= 1 && rows < (1L << 31) && D >= 1, "lmkd_ctx_ln_fwd: %ld rows of %d", rows, D);
   LMKD_REQUIRE(Kraw && gamma && beta && Kn, "lmkd_ctx_ln_fwd: null pointer");
-  hipLaunchKernelGGL(ctx_ln_fwd_kernel, dim3((unsigned)rows), dim3(CX_THREADS), 0, (hipStream_t)stream, Kraw, gamma, beta, Kn, Khat, rstd, D,
-                     eps);
+  hipLaunchKernelGGL((ln_fwd_kernel<false, true>), dim3((unsigned)rows), dim3(ROW_THREADS), 0, (hipStream_t)stream, Kraw, (const float*)nullptr, 0L,
+                     gamma, beta, (const float*)nullptr, Kn, (long)D, Khat, rstd, D, eps);
   LMKD_CHECK_LAUNCH("lmkd_ctx_ln_fwd");
   return LMKD_OK;
 }

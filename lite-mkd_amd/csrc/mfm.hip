@@ -1,143 +1,25 @@
-// MFM teacher-feature fusion (teacher/code/model.py:1135-1151,1300-1331,1361-1392,1648-1664), inference only:
-// the pieces of nn.TransformerEncoderLayer (post-norm, ReLU FFN) that are not GEMMs.  The GEMMs (in_proj, out_proj,
-// linear1+ReLU, linear2, f1) run on lmkd_gemm_f32.
-#include "common.h"
+// MFM teacher-feature fusion (teacher/code/model.py:1135-1151,1300-1331,1361-1392,1648-1664), inference and training: the pieces of
+// nn.TransformerEncoderLayer (post-norm, ReLU FFN) that are not GEMMs - LayerNorm (csrc/rows.h) and the 8-token attention, forward and
+// backward.  The GEMMs (in_proj, out_proj, linear1+ReLU, linear2, f1) run on lmkd_gemm_f32.  fp32, one workgroup per row / per
+// (sequence, head), every sum in a fixed order: no atomics, two calls give the same bits.
+#include "rows.h"
 
-#define MF_THREADS 256
+#define MF_THREADS ROW_THREADS
 
 // y[r, col_off : col_off+D] (row stride ldy) = LayerNorm(x[r,:] (+ res[r % res_rows, :])) * gamma + beta
-__global__ void layernorm_fwd_kernel(const float* __restrict__ x, const float* __restrict__ res, long res_rows,
-                                     const float* __restrict__ gamma, const float* __restrict__ beta, float* __restrict__ y,
-                                     long ldy, int D, float eps) {
-  __shared__ float red[4];
-  extern __shared__ float row[];
-  const long r = blockIdx.x;
-  const float* xr = x + r * D;
-  const float* rr = res ? res + (r % res_rows) * D : nullptr;
-  float s = 0.f;
-  for (int d = threadIdx.x; d < D; d += MF_THREADS) {
-    const float v = xr[d] + (rr ? rr[d] : 0.f);
-    row[d] = v;
-    s += v;
-  }
-  const float mean = block_sum_256(s, red) / (float)D;
-  float q = 0.f;
-  for (int d = threadIdx.x; d < D; d += MF_THREADS) { const float c = row[d] - mean; q += c * c; }
-  const float rstd = 1.f / sqrtf(block_sum_256(q, red) / (float)D + eps);
-  float* yr = y + r * ldy;
-  for (int d = threadIdx.x; d < D; d += MF_THREADS) yr[d] = (row[d] - mean) * rstd * gamma[d] + beta[d];
-}
-
 extern "C" int lmkd_layernorm_fwd(const float* x, const float* res, long res_rows, const float* gamma, const float* beta, float* y,
                                   long ldy, long rows, int D, float eps, void* stream) {
   LMKD_REQUIRE(x && gamma && beta && y && rows > 0 && D > 0 && ldy >= D, "lmkd_layernorm_fwd: bad arguments");
   LMKD_REQUIRE(!res || res_rows > 0, "lmkd_layernorm_fwd: res_rows must be positive");
   LMKD_REQUIRE((size_t)D * sizeof(float) <= 96 * 1024, "lmkd_layernorm_fwd: row of %d floats does not fit in LDS", D);
-  hipLaunchKernelGGL(layernorm_fwd_kernel, dim3((unsigned)rows), dim3(MF_THREADS), (size_t)D * sizeof(float), (hipStream_t)stream, x,
-                     res, res_rows, gamma, beta, y, ldy, D, eps);
-  LMKD_CHECK_LAUNCH("layernorm_fwd_kernel");
+  hipLaunchKernelGGL((ln_fwd_kernel<true, false>), dim3((unsigned)rows), dim3(ROW_THREADS), (size_t)D * sizeof(float), (hipStream_t)stream, x,
+                     res, res_rows, gamma, beta, (const float*)nullptr, y, ldy, (float*)nullptr, (float*)nullptr, D, eps);
+  LMKD_CHECK_LAUNCH("ln_fwd_kernel");
   return LMKD_OK;
 }
 
-// Self-attention over L <= 8 tokens per (sequence, head): qkv [B*L, 3*D] (q | k | v), out [B*L, D], head dim hd = D/H.
-__global__ void mha_small_kernel(const float* __restrict__ qkv, float* __restrict__ out, int L, int D, int H, float scale) {
-  __shared__ float part[4][64];
-  __shared__ float P[64];
-  const int b = blockIdx.x / H, h = blockIdx.x % H;
-  const int hd = D / H;
-  const float* base = qkv + (long)b * L * 3 * D + h * hd;
-  float acc[64];
-#pragma unroll
-  for (int e = 0; e < 64; ++e) acc[e] = 0.f;
-  for (int d = threadIdx.x; d < hd; d += MF_THREADS) {
-    float q[8], k[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      q[i] = i < L ? base[(long)i * 3 * D + d] : 0.f;
-      k[i] = i < L ? base[(long)i * 3 * D + D + d] : 0.f;
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) acc[i * 8 + j] = fmaf(q[i], k[j], acc[i * 8 + j]);
-  }
-#pragma unroll
-  for (int e = 0; e < 64; ++e) {
-    const float v = wave_sum(acc[e]);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6][e] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < 64) P[threadIdx.x] = (part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x]) * scale;
-  __syncthreads();
-  if (threadIdx.x < L) {
-    const int i = threadIdx.x;
-    float m = -INFINITY;
-    for (int j = 0; j < L; ++j) m = fmaxf(m, P[i * 8 + j]);
-    float z = 0.f;
-    for (int j = 0; j < L; ++j) { const float e = expf(P[i * 8 + j] - m); P[i * 8 + j] = e; z += e; }
-    for (int j = 0; j < L; ++j) P[i * 8 + j] /= z;
-  }
-  __syncthreads();
-  float* ob = out + (long)b * L * D + h * hd;
-  for (int d = threadIdx.x; d < hd; d += MF_THREADS) {
-    float v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = j < L ? base[(long)j * 3 * D + 2 * D + d] : 0.f;
-    for (int i = 0; i < L; ++i) {
-      float o = 0.f;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) o = fmaf(P[i * 8 + j], v[j], o);
-      ob[(long)i * D + d] = o;
-    }
-  }
-}
-
-extern "C" int lmkd_mha_small(const float* qkv, float* out, int B, int L, int D, int H, void* stream) {
-  LMKD_REQUIRE(qkv && out && B > 0 && L > 0 && L <= 8 && H > 0 && D % H == 0, "lmkd_mha_small: bad arguments (L <= 8)");
-  hipLaunchKernelGGL(mha_small_kernel, dim3(B * H), dim3(MF_THREADS), 0, (hipStream_t)stream, qkv, out, L, D, H,
-                     1.f / sqrtf((float)(D / H)));
-  LMKD_CHECK_LAUNCH("mha_small_kernel");
-  return LMKD_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// Training (model.py:1143-1151 TrainablePositionalEncoding.forward, :1317-1323 ThreeTransforTemproal.forward, :1376-1385
-// TwoTransforFusion.forward): the same two pieces with what their backward reads, and the backward.  fp32, one workgroup per row /
-// per (sequence, head), every sum in a fixed order: no atomics, two calls give the same bits.
-// ---------------------------------------------------------------------------------------------------------------------------
-
-// layernorm_fwd_kernel + xhat [rows, D], rstd [rows]; y *= mask[r, :] (the dropout of :1150; nullable)
-__global__ void layernorm_train_fwd_kernel(const float* __restrict__ x, const float* __restrict__ res, long res_rows,
-                                           const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ mask,
-                                           float* __restrict__ y, long ldy, float* __restrict__ xhat, float* __restrict__ rstd_out, int D,
-                                           float eps) {
-  __shared__ float red[4];
-  extern __shared__ float row[];
-  const long r = blockIdx.x;
-  const float* xr = x + r * D;
-  const float* rr = res ? res + (r % res_rows) * D : nullptr;
-  float s = 0.f;
-  for (int d = threadIdx.x; d < D; d += MF_THREADS) {
-    const float v = xr[d] + (rr ? rr[d] : 0.f);
-    row[d] = v;
-    s += v;
-  }
-  const float mean = block_sum_256(s, red) / (float)D;
-  float q = 0.f;
-  for (int d = threadIdx.x; d < D; d += MF_THREADS) { const float c = row[d] - mean; q += c * c; }
-  const float rstd = 1.f / sqrtf(block_sum_256(q, red) / (float)D + eps);
-  float* yr = y + r * ldy;
-  float* hr = xhat + r * D;
-  const float* mr = mask ? mask + r * D : nullptr;
-  for (int d = threadIdx.x; d < D; d += MF_THREADS) {
-    const float h = (row[d] - mean) * rstd;
-    hr[d] = h;
-    const float v = h * gamma[d] + beta[d];
-    yr[d] = mr ? v * mr[d] : v;
-  }
-  if (threadIdx.x == 0) rstd_out[r] = rstd;
-}
-
+// the same with what the backward reads, xhat [rows, D] and rstd [rows] (model.py:1143-1151 TrainablePositionalEncoding.forward,
+// :1317-1323 ThreeTransforTemproal.forward, :1376-1385 TwoTransforFusion.forward); y *= mask[r, :] (the dropout of :1150; nullable)
 extern "C" int lmkd_layernorm_train_fwd(const float* x, const float* res, long res_rows, const float* gamma, const float* beta,
                                         const float* mask, float* y, long ldy, float* xhat, float* rstd, long rows, int D, float eps,
                                         void* stream) {
@@ -146,38 +28,14 @@ extern "C" int lmkd_layernorm_train_fwd(const float* x, const float* res, long r
   LMKD_REQUIRE(!res || res_rows > 0, "lmkd_layernorm_train_fwd: res_rows must be positive");
   LMKD_REQUIRE((size_t)D * sizeof(float) <= 96 * 1024, "lmkd_layernorm_train_fwd: row of %d floats does not fit in LDS", D);
   LMKD_REQUIRE(x && gamma && beta && y && xhat && rstd, "lmkd_layernorm_train_fwd: null pointer");
-  hipLaunchKernelGGL(layernorm_train_fwd_kernel, dim3((unsigned)rows), dim3(MF_THREADS), (size_t)D * sizeof(float), (hipStream_t)stream,
-                     x, res, res_rows, gamma, beta, mask, y, ldy, xhat, rstd, D, eps);
-  LMKD_CHECK_LAUNCH("layernorm_train_fwd_kernel");
+  hipLaunchKernelGGL((ln_fwd_kernel<true, true>), dim3((unsigned)rows), dim3(ROW_THREADS), (size_t)D * sizeof(float), (hipStream_t)stream, x,
+                     res, res_rows, gamma, beta, mask, y, ldy, xhat, rstd, D, eps);
+  LMKD_CHECK_LAUNCH("ln_fwd_kernel");
   return LMKD_OK;
 }
 
-// v = dy[r, :] (row stride lddy) o mask[r, :] ; g = v o gamma ; dpre[r, :] = rstd[r] (g - mean(g) - xhat[r, :] mean(g o xhat)) ; dyc = v
-__global__ void layernorm_train_bwd_kernel(const float* __restrict__ dy, long lddy, const float* __restrict__ mask,
-                                           const float* __restrict__ xhat, const float* __restrict__ rstd, const float* __restrict__ gamma,
-                                           float* __restrict__ dpre, float* __restrict__ dyc, int D) {
-  __shared__ float red[4];
-  const long r = blockIdx.x;
-  const float* gr = dy + r * lddy;
-  const float* mr = mask ? mask + r * D : nullptr;
-  const float* h = xhat + r * D;
-  float s1 = 0.f, s2 = 0.f;
-  for (int d = threadIdx.x; d < D; d += MF_THREADS) {
-    const float v = mr ? gr[d] * mr[d] : gr[d];
-    if (dyc) dyc[r * D + d] = v;
-    const float g = v * gamma[d];
-    s1 += g;
-    s2 += g * h[d];
-  }
-  const float m1 = block_sum_256(s1, red) / (float)D;
-  const float m2 = block_sum_256(s2, red) / (float)D;
-  const float rs = rstd[r];
-  for (int d = threadIdx.x; d < D; d += MF_THREADS) {
-    const float v = mr ? gr[d] * mr[d] : gr[d];
-    dpre[r * D + d] = rs * (v * gamma[d] - m1 - h[d] * m2);
-  }
-}
-
+// dpre[r, :] = the gradient of that LayerNorm's input from dy[r, :] (row stride lddy) ; dyc[r, :] = dy[r, :] o mask[r, :] (nullable), the
+// operand of the dgamma / dbeta column sums
 extern "C" int lmkd_layernorm_train_bwd(const float* dy, long lddy, const float* mask, const float* xhat, const float* rstd,
                                         const float* gamma, float* dpre, float* dyc, long rows, int D, void* stream) {
   LMKD_REQUIRE(rows > 0 && D > 0, "lmkd_layernorm_train_bwd: %ld rows of %d", rows, D);
@@ -185,19 +43,23 @@ extern "C" int lmkd_layernorm_train_bwd(const float* dy, long lddy, const float*
   LMKD_REQUIRE((size_t)D * sizeof(float) <= 96 * 1024, "lmkd_layernorm_train_bwd: row of %d floats is past the forward's limit", D);
   LMKD_REQUIRE(dy && xhat && rstd && gamma && dpre, "lmkd_layernorm_train_bwd: null pointer");
   LMKD_REQUIRE(dpre != dy && dyc != dy, "lmkd_layernorm_train_bwd: the outputs may not alias dy (it is read twice)");
-  hipLaunchKernelGGL(layernorm_train_bwd_kernel, dim3((unsigned)rows), dim3(MF_THREADS), 0, (hipStream_t)stream, dy, lddy, mask, xhat,
-                     rstd, gamma, dpre, dyc, D);
-  LMKD_CHECK_LAUNCH("layernorm_train_bwd_kernel");
+  hipLaunchKernelGGL(ln_bwd_kernel<false>, dim3((unsigned)rows), dim3(ROW_THREADS), 0, (hipStream_t)stream, dy, lddy, mask, xhat, rstd, gamma, dpre,
+                     dyc, D);
+  LMKD_CHECK_LAUNCH("ln_bwd_kernel");
   return LMKD_OK;
 }
 
-// mha_small_kernel that keeps the probabilities: Pout [B*H, 8, 8] (before dropout; zero beyond L), and multiplies them by
-// mask [B*H, L, L] (nullable) on their way to V - the dropout inside nn.MultiheadAttention
-__global__ void mha_small_train_fwd_kernel(const float* __restrict__ qkv, const float* __restrict__ mask, float* __restrict__ out,
-                                           float* __restrict__ Pout, int L, int D, int H, float scale) {
+// Self-attention over L <= 8 tokens per (sequence, head): qkv [B*L, 3*D] (q | k | v), out [B*L, D], head dim hd = D/H.
+// KEEP (training) keeps the probabilities: Pout [B*H, 8, 8] (before dropout; zero beyond L), and multiplies them by mask [B*H, L, L]
+// (nullable) on their way to V - the dropout inside nn.MultiheadAttention.  The loops over private arrays are unrolled over 8 tokens
+// (with guards where they load): none is indexed dynamically.
+template <bool KEEP>
+__global__ void mha_small_fwd_kernel(const float* __restrict__ qkv, const float* __restrict__ mask, float* __restrict__ out,
+                                     float* __restrict__ Pout, int L, int D, int H, float scale) {
   __shared__ float part[4][64];
   __shared__ float P[64];
-  __shared__ float PM[64];
+  __shared__ float PMk[KEEP ? 64 : 1];
+  const float* PM = KEEP ? PMk : P;      // what meets V: P o mask, or P itself
   const int b = blockIdx.x / H, h = blockIdx.x % H;
   const int hd = D / H;
   const float* base = qkv + (long)b * L * 3 * D + h * hd;
@@ -233,26 +95,35 @@ __global__ void mha_small_train_fwd_kernel(const float* __restrict__ qkv, const 
     for (int j = 0; j < L; ++j) P[i * 8 + j] /= z;
   }
   __syncthreads();
-  if (threadIdx.x < 64) {      // rows and columns beyond L hold the zero scores of their zero operands
-    const int i = threadIdx.x >> 3, j = threadIdx.x & 7;
-    const float p = P[threadIdx.x];
-    Pout[(long)blockIdx.x * 64 + threadIdx.x] = p;
-    PM[threadIdx.x] = (mask && i < L && j < L) ? p * mask[((long)blockIdx.x * L + i) * L + j] : p;
+  if constexpr (KEEP) {
+    if (threadIdx.x < 64) {      // rows and columns beyond L hold the zero scores of their zero operands
+      const int i = threadIdx.x >> 3, j = threadIdx.x & 7;
+      const float p = P[threadIdx.x];
+      Pout[(long)blockIdx.x * 64 + threadIdx.x] = p;
+      PMk[threadIdx.x] = (mask && i < L && j < L) ? p * mask[((long)blockIdx.x * L + i) * L + j] : p;
+    }
+    __syncthreads();
   }
-  __syncthreads();
   float* ob = out + (long)b * L * D + h * hd;
   for (int d = threadIdx.x; d < hd; d += MF_THREADS) {
     float v[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = j < L ? base[(long)j * 3 * D + 2 * D + d] : 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
+    for (int i = 0; i < L; ++i) {
       float o = 0.f;
 #pragma unroll
       for (int j = 0; j < 8; ++j) o = fmaf(PM[i * 8 + j], v[j], o);
-      if (i < L) ob[(long)i * D + d] = o;
+      ob[(long)i * D + d] = o;
     }
   }
+}
+
+extern "C" int lmkd_mha_small(const float* qkv, float* out, int B, int L, int D, int H, void* stream) {
+  LMKD_REQUIRE(qkv && out && B > 0 && L > 0 && L <= 8 && H > 0 && D % H == 0, "lmkd_mha_small: bad arguments (L <= 8)");
+  hipLaunchKernelGGL(mha_small_fwd_kernel<false>, dim3(B * H), dim3(MF_THREADS), 0, (hipStream_t)stream, qkv, (const float*)nullptr, out,
+                     (float*)nullptr, L, D, H, 1.f / sqrtf((float)(D / H)));
+  LMKD_CHECK_LAUNCH("mha_small_fwd_kernel");
+  return LMKD_OK;
 }
 
 static int mha_small_check(const char* who, int B, int L, int D, int H) {
@@ -267,9 +138,9 @@ extern "C" int lmkd_mha_small_train_fwd(const float* qkv, const float* mask, flo
                                         void* stream) {
   if (int rc = mha_small_check("lmkd_mha_small_train_fwd", B, L, D, H)) return rc;
   LMKD_REQUIRE(qkv && out && P, "lmkd_mha_small_train_fwd: null pointer");
-  hipLaunchKernelGGL(mha_small_train_fwd_kernel, dim3(B * H), dim3(MF_THREADS), 0, (hipStream_t)stream, qkv, mask, out, P, L, D, H,
+  hipLaunchKernelGGL(mha_small_fwd_kernel<true>, dim3(B * H), dim3(MF_THREADS), 0, (hipStream_t)stream, qkv, mask, out, P, L, D, H,
                      1.f / sqrtf((float)(D / H)));
-  LMKD_CHECK_LAUNCH("mha_small_train_fwd_kernel");
+  LMKD_CHECK_LAUNCH("mha_small_fwd_kernel");
   return LMKD_OK;
 }
 

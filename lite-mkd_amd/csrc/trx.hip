@@ -6,9 +6,10 @@
 //   (per-frame projections; the reference's c*2048-wide tuple Linear, c = 2 frame pairs or 3 frame triples, is the
 //   sum of c 2048-wide slices) -> tuple combine + LayerNorm(K) -> scores GEMM -> per-class softmax -> P*V GEMM ->
 //   squared distance.
-#include "common.h"
+#include "rows.h"
 
 #define TX_THREADS 256
+static_assert(TX_THREADS == ROW_THREADS, "trx_tuples_ln_fwd_kernel runs the row LayerNorm of rows.h");
 #define LMKD_MAX_SEG 16
 struct Segs {
   int n;
@@ -140,26 +141,19 @@ __global__ void trx_tuples_ln_fwd_kernel(const float* __restrict__ P, const floa
 #pragma unroll
   for (int s = 0; s < CARD; ++s) pf[s] = P + (long)(n * L + f[s]) * 2 * CARD * D;
   const long orow = (long)(rowmap ? rowmap[n] : n) * T + t;
-  float s = 0.f;
-  for (int d = threadIdx.x; d < D; d += TX_THREADS) {
+  auto gather = [&](int d) {      // the tuple's key element, staged; its value element goes out on the way
     float k = pf[0][d] + pf[1][D + d];
     float v = pf[0][CARD * D + d] + pf[1][(CARD + 1) * D + d];
     if (CARD == 3) { k += pf[CARD - 1][2 * D + d]; v += pf[CARD - 1][(CARD + 2) * D + d]; }
     k += bk[d];
     kraw[d] = k;
-    s += k;
     V[orow * D + d] = v + bv[d];
-  }
-  const float mean = block_sum_256(s, red) / (float)D;
-  float q = 0.f;
-  for (int d = threadIdx.x; d < D; d += TX_THREADS) { const float c = kraw[d] - mean; q += c * c; }
-  const float var = block_sum_256(q, red) / (float)D;
-  const float rstd = 1.f / sqrtf(var + eps);
-  for (int d = threadIdx.x; d < D; d += TX_THREADS) {
-    const float h = (kraw[d] - mean) * rstd;
-    if (Khat) Khat[orow * D + d] = h;
-    Kn[orow * D + d] = h * gamma[d] + beta[d];
-  }
+    return k;
+  };
+  auto at = [&](int d) { return kraw[d]; };
+  float mean, rstd;
+  row_stats(gather, at, D, eps, red, mean, rstd);
+  row_norm_store(at, D, mean, rstd, gamma, beta, nullptr, Kn + orow * D, Khat ? Khat + orow * D : nullptr);
   if (threadIdx.x == 0 && rstd_out) rstd_out[orow] = rstd;
 }
 
@@ -200,30 +194,13 @@ extern "C" int lmkd_trx_tuples_ln_fwd(const float* P, const float* bk, const flo
   return trx_tuples_ln_fwd_launch(P, bk, bv, gamma, beta, rowmap, tuples, Kn, Khat, V, rstd, NV, L, card, T, D, eps, stream);
 }
 
-// LayerNorm backward per row (in place: dKn -> dKraw):  dxh = dKn*gamma ;
-//   dKraw = rstd*(dxh - mean(dxh) - Khat*mean(dxh*Khat))
-__global__ void ln_bwd_rows_kernel(float* __restrict__ dK, const float* __restrict__ Khat, const float* __restrict__ rstd,
-                                   const float* __restrict__ gamma, int D) {
-  __shared__ float red[4];
-  const long r = blockIdx.x;
-  float* g = dK + r * D;
-  const float* h = Khat + r * D;
-  float s1 = 0.f, s2 = 0.f;
-  for (int d = threadIdx.x; d < D; d += TX_THREADS) {
-    const float v = g[d] * gamma[d];
-    s1 += v;
-    s2 += v * h[d];
-  }
-  const float m1 = block_sum_256(s1, red) / (float)D;
-  const float m2 = block_sum_256(s2, red) / (float)D;
-  const float rs = rstd[r];
-  for (int d = threadIdx.x; d < D; d += TX_THREADS) g[d] = rs * (g[d] * gamma[d] - m1 - h[d] * m2);
-}
+// LayerNorm backward per row, in place (dKn -> dKraw): the kernel of csrc/rows.h with its output on its input
 extern "C" int lmkd_layernorm_bwd_rows(float* dK_inout, const float* Khat, const float* rstd, const float* gamma, long rows, int D,
                                        void* stream) {
   LMKD_REQUIRE(dK_inout && Khat && rstd && gamma && rows > 0 && D > 0, "lmkd_layernorm_bwd_rows: bad arguments");
-  hipLaunchKernelGGL(ln_bwd_rows_kernel, dim3((unsigned)rows), dim3(TX_THREADS), 0, (hipStream_t)stream, dK_inout, Khat, rstd, gamma, D);
-  LMKD_CHECK_LAUNCH("ln_bwd_rows_kernel");
+  hipLaunchKernelGGL(ln_bwd_kernel<true>, dim3((unsigned)rows), dim3(ROW_THREADS), 0, (hipStream_t)stream, (const float*)nullptr, (long)D,
+                     (const float*)nullptr, Khat, rstd, gamma, dK_inout, (float*)nullptr, D);
+  LMKD_CHECK_LAUNCH("ln_bwd_kernel");
   return LMKD_OK;
 }
 

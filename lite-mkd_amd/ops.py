@@ -310,21 +310,10 @@ class LinearFn(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             dx = _empty((M, K), x)
             gemm("K", "N", M, K, N, dy, N, w, K, dx, K, k_block=ctx.k_block)          # dx = dy @ W
-        if ctx.needs_input_grad[1]:
-            tw = _grad_target(w)
-            if side_accumulate(w, lambda t: gemm("M", "N", N, K, M, dy, N, x, K, t, K, beta=1.0), dy, x):
-                pass
-            elif tw is not None:      # w.grad += dy^T @ x in the GEMM's epilogue (beta = 1)
-                gemm("M", "N", N, K, M, dy, N, x, K, tw, K, beta=1.0)
-            else:
-                dw = _empty((N, K), x)
-                gemm("M", "N", N, K, M, dy, N, x, K, dw, K)          # dW = dy^T @ x
+        if ctx.needs_input_grad[1]:          # dW = dy^T @ x
+            dw = deliver_wgrad(w, lambda t, beta: gemm("M", "N", N, K, M, dy, N, x, K, t, K, beta=beta), (N, K), dy, x)
         if ctx.has_bias and ctx.needs_input_grad[2]:
-            tb = _grad_target(ctx.bias)
-            if tb is not None:
-                colsum(dy, out=tb, accumulate=True)
-            else:
-                db = colsum(dy)
+            db = deliver_colsum(ctx.bias, dy)
         return dx, dw, db, None
 
 
@@ -381,19 +370,9 @@ class TwoHeadLinearFn(torch.autograd.Function):
             dw = db = None
             if g is not None:
                 if pw.requires_grad:
-                    if not side_accumulate(pw, lambda t, g=g: gemm("M", "N", N, K, M, g, N, X, K, t, K, beta=1.0), g, X):
-                        tw = _grad_target(pw)
-                        if tw is not None:
-                            gemm("M", "N", N, K, M, g, N, X, K, tw, K, beta=1.0)
-                        else:
-                            dw = _empty((N, K), X)
-                            gemm("M", "N", N, K, M, g, N, X, K, dw, K)
+                    dw = deliver_wgrad(pw, lambda t, beta, g=g: gemm("M", "N", N, K, M, g, N, X, K, t, K, beta=beta), (N, K), g, X)
                 if pb is not None and pb.requires_grad:
-                    tb = _grad_target(pb)
-                    if tb is not None:
-                        colsum(g, out=tb, accumulate=True)
-                    else:
-                        db = colsum(g)
+                    db = deliver_colsum(pb, g)
             outs += [dw, db]
         return tuple(outs)
 
@@ -1030,6 +1009,32 @@ def side_accumulate(param, fn, *reads):
         return False
     _on_wgrad_stream(param.device, lambda: fn(param.grad), reads)
     return True
+
+
+# A parameter gradient reaches its parameter one of three ways, tried in this order: added into .grad on the weight-gradient stream
+# (side_accumulate), added into .grad or its shadow on the caller's stream (_grad_target), or returned to autograd as a fresh tensor.
+def deliver_wgrad(param, launch, shape, *reads):
+    """the weight gradient launch(target, beta) computes with a gemm (beta = 1 adds to the target); shape: the gradient's; reads: the tensors
+    the launch reads.  -> None after accumulating it directly, else the fresh gradient tensor"""
+    if side_accumulate(param, lambda t: launch(t, 1.0), *reads):
+        return None
+    t = _grad_target(param)
+    if t is not None:
+        launch(t, 1.0)
+        return None
+    dw = _empty(shape, reads[0])
+    launch(dw, 0.0)
+    return dw
+
+
+def deliver_colsum(param, a, b=None):
+    """the column-sum gradient sum_r a[r, :] (* b[r, :]) of a bias / LayerNorm parameter: -> None after accumulating it directly, else the
+    fresh gradient tensor.  (It feeds nothing and is small: never on the weight-gradient stream.)"""
+    t = _grad_target(param)
+    if t is None:
+        return colsum(a, b)
+    colsum(a, b, out=t, accumulate=True)
+    return None
 
 
 def weight_grad(w, x, dy, stride, pad, pre_stats=None, seg=0):
@@ -2288,6 +2293,16 @@ def _trx_forward(sup, qry, plan, wk, bk, wv, bv, gamma, beta, pe, mask, want_gra
     return logits, saved
 
 
+def _trx_keep(ctx, saved, sup, qry, wk, bk, wv, bv, gamma, beta, mask, plan, *more):
+    """what _trx_backward reads, kept on ctx (saved: _trx_forward's; more: further tensors to save behind the twelve)"""
+    Xp, Kn, V, Khat, rstd, S, proto, rowmap, seg_off, seg_cnt = saved
+    ctx.save_for_backward(Xp, Kn, V, Khat, rstd, S, proto, rowmap, wk, wv, gamma, mask, *more)
+    ctx.plan, ctx.seg_off, ctx.seg_cnt = plan, seg_off, seg_cnt
+    ctx.shapes = (sup.shape, qry.shape)
+    ctx.biases = (bk, bv, beta)
+    ctx.wkv = (wk, wv)      # the parameter OBJECTS (saved tensors come back as other Python objects): identity keys of the caches
+
+
 class TRXLogitsFn(torch.autograd.Function):
     """TemporalCrossTransformer.forward (TRX_2fcsup.py:74-148) for one head."""
 
@@ -2295,12 +2310,7 @@ class TRXLogitsFn(torch.autograd.Function):
     def forward(ctx, sup, qry, wk, bk, wv, bv, gamma, beta, pe, mask, plan, k_block=0):
         _chk(sup, qry, wk, bk, wv, bv, gamma, beta, pe, mask)
         logits, saved = _trx_forward(sup.contiguous(), qry.contiguous(), plan, wk, bk, wv, bv, gamma, beta, pe, mask, True, k_block)
-        Xp, Kn, V, Khat, rstd, S, proto, rowmap, seg_off, seg_cnt = saved
-        ctx.save_for_backward(Xp, Kn, V, Khat, rstd, S, proto, rowmap, wk, wv, gamma, mask)
-        ctx.plan, ctx.seg_off, ctx.seg_cnt = plan, seg_off, seg_cnt
-        ctx.shapes = (sup.shape, qry.shape)
-        ctx.biases = (bk, bv, beta)
-        ctx.wkv = (wk, wv)      # the parameter OBJECTS (saved tensors come back as other Python objects): identity keys of the caches
+        _trx_keep(ctx, saved, sup, qry, wk, bk, wv, bv, gamma, beta, mask, plan)
         ctx.k_block = k_block
         return logits
 
@@ -2308,6 +2318,16 @@ class TRXLogitsFn(torch.autograd.Function):
     def backward(ctx, g):
         _audit.engine_owned(g)
         return _trx_backward(ctx, g) + (None,)
+
+
+def _kv_norm_backward(dKn, dV, Khat, rstd, gamma, bk, bv, beta):
+    """the middle of both K/V heads' backward (TRX, CTX): the key LayerNorm's parameter gradients, dKn -> dKraw in place, the two projection
+    bias gradients.  -> dgamma, dbeta, dbk, dbv, each None where deliver_colsum accumulated it directly"""
+    rows, D = dKn.shape
+    dgamma = deliver_colsum(gamma, dKn, Khat)
+    dbeta = deliver_colsum(beta, dKn)
+    lib().call("lmkd_layernorm_bwd_rows", _p(dKn), _p(Khat), _p(rstd), _p(gamma), rows, D, _stream())
+    return dgamma, dbeta, deliver_colsum(bk, dKn), deliver_colsum(bv, dV)
 
 
 def _trx_backward(ctx, g, gsim=None, gram=None):
@@ -2353,21 +2373,7 @@ def _trx_backward(ctx, g, gsim=None, gram=None):
         sc = 1.0 / math.sqrt(D)
         gemm("K", "N", Rq, D, Rs, dS, Rs, Sk, D, dQk, D, alpha=sc)                                        # dQk = sc * dS @ Sk
         gemm("M", "N", Rs, D, Rq, dS, Rs, Qk, D, dSk, D, alpha=sc)                                        # dSk = sc * dS^T @ Qk
-        # parameter gradients: returned to autograd, or (DIRECT_PARAM_GRAD) added into the parameters' .grad by the kernels themselves
-        bk_, bv_, beta_ = getattr(ctx, "biases", (None, None, None))
-
-        def colsum_into(param, a, b=None):
-            t = _grad_target(param)
-            if t is None:
-                return colsum(a, b)
-            colsum(a, b, out=t, accumulate=True)
-            return None
-        # LayerNorm parameter grads, then dKn -> dKraw in place
-        dgamma = colsum_into(gamma, dKn, Khat)
-        dbeta = colsum_into(beta_, dKn)
-        lib().call("lmkd_layernorm_bwd_rows", _p(dKn), _p(Khat), _p(rstd), _p(gamma), rows, D, _stream())
-        dbk = colsum_into(bk_, dKn)
-        dbv = colsum_into(bv_, dV)
+        dgamma, dbeta, dbk, dbv = _kv_norm_backward(dKn, dV, Khat, rstd, gamma, *getattr(ctx, "biases", (None, None, None)))
         dP = _empty((NV * L, PW), Xp)
         if card == 2:
             lib().call("lmkd_trx_tuple_bwd_gather", _p(dKn), _p(dV), _p(rowmap), _p(dP), NV, L, D, _stream())
@@ -2375,17 +2381,9 @@ def _trx_backward(ctx, g, gsim=None, gram=None):
             lib().call("lmkd_trx_tuples_bwd_gather", _p(dKn), _p(dV), _p(rowmap), _p(trx_tuple_table(L, card, Xp.device)), _p(dP), NV, L,
                        card, T, D, _stream())
         # weight grads: dW[:, slot] = dP[:, blk]^T @ Xp
-        dwk = dwv = None
-        if not side_accumulate(wk, lambda t: gemm("M", "N", D, Din, NV * L, dP, PW, Xp, Din, t, card * Din, batch=card, sA=D, sC=Din, beta=1.0), dP, Xp):
-            tk = _grad_target(wk)
-            dwk = _empty((D, card * Din), Xp) if tk is None else None
-            gemm("M", "N", D, Din, NV * L, dP, PW, Xp, Din, dwk if tk is None else tk, card * Din, batch=card, sA=D, sC=Din, beta=0.0 if tk is None else 1.0)
-        if not side_accumulate(wv, lambda t: gemm("M", "N", D, Din, NV * L, dP, PW, Xp, Din, t, card * Din, batch=card, sA=D, sC=Din, A_off=card * D,
-                                                   beta=1.0), dP, Xp):
-            tv = _grad_target(wv)
-            dwv = _empty((D, card * Din), Xp) if tv is None else None
-            gemm("M", "N", D, Din, NV * L, dP, PW, Xp, Din, dwv if tv is None else tv, card * Din, batch=card, sA=D, sC=Din, A_off=card * D,
-                 beta=0.0 if tv is None else 1.0)
+        dwk, dwv = (deliver_wgrad(w, lambda t, beta, off=off: gemm("M", "N", D, Din, NV * L, dP, PW, Xp, Din, t, card * Din, batch=card, sA=D, sC=Din,
+                                                                    A_off=off, beta=beta), (D, card * Din), dP, Xp)
+                    for w, off in ((wk, 0), (wv, card * D)))
         # input grads: dXp = sum_blk dP[:, blk] @ W[:, slot]
         dX = _empty((NV * L, Din), Xp)
         packs = None
@@ -2425,11 +2423,7 @@ class TRXSupFn(torch.autograd.Function):
         Xp, Kn, V, Khat, rstd, S, proto, rowmap, seg_off, seg_cnt = saved
         L, D = sup.shape[1], wk.shape[0]
         sim, gram = _trx_sup_sim(proto, plan, qry.shape[0], math.comb(L, wk.shape[1] // sup.shape[2]), D)
-        ctx.save_for_backward(Xp, Kn, V, Khat, rstd, S, proto, rowmap, wk, wv, gamma, mask, gram)
-        ctx.plan, ctx.seg_off, ctx.seg_cnt = plan, seg_off, seg_cnt
-        ctx.shapes = (sup.shape, qry.shape)
-        ctx.biases = (bk, bv, beta)
-        ctx.wkv = (wk, wv)
+        _trx_keep(ctx, saved, sup, qry, wk, bk, wv, bv, gamma, beta, mask, plan, gram)
         return logits, sim
 
     @staticmethod
@@ -2658,7 +2652,7 @@ def _ctx_forward(sup, qry, plan, wk, bk, wv, bv, gamma, beta, pe, mask, want_gra
 
 class CtxLogitsFn(torch.autograd.Function):
     """CrossTransformer.forward (teacher/code/model.py:2859-2924): the frame-level cross-transformer head, csrc/ctx.hip, DESIGN.md 18.
-    Parameter gradients follow TRXLogitsFn: added into .grad by the kernels where DIRECT_PARAM_GRAD allows it, else returned."""
+    Parameter gradients go the way of TRXLogitsFn's, through deliver_wgrad / deliver_colsum."""
 
     @staticmethod
     def forward(ctx, sup, qry, wk, bk, wv, bv, gamma, beta, pe, mask, plan):
@@ -2683,27 +2677,9 @@ class CtxLogitsFn(torch.autograd.Function):
         dKn, dV = _empty((rows, D), Xp), _empty((rows, D), Xp)
         lib().call("lmkd_ctx_attend_bwd", _p(g.contiguous()), _p(Kn), _p(V), _p(plan.order), _p(A), _p(dS), _p(E), _p(dKn), _p(dV), Ns, Nq, plan.way,
                    L, D, nseg, seg_off, seg_cnt, seg_col, _stream())
-        bk_, bv_, beta_ = ctx.biases
-
-        def colsum_into(param, a, b=None):
-            t = _grad_target(param)
-            if t is None:
-                return colsum(a, b)
-            colsum(a, b, out=t, accumulate=True)
-            return None
-        dgamma = colsum_into(gamma, dKn, Khat)
-        dbeta = colsum_into(beta_, dKn)
-        lib().call("lmkd_layernorm_bwd_rows", _p(dKn), _p(Khat), _p(rstd), _p(gamma), rows, D, _stream())      # dKn -> dKraw in place
-        dbk = colsum_into(bk_, dKn)
-        dbv = colsum_into(bv_, dV)
-        grads = []
-        for w, dy in ((wk, dKn), (wv, dV)):      # dW = dy^T Xp
-            dw = None
-            if not side_accumulate(w, lambda t, dy=dy: gemm("M", "N", D, Din, rows, dy, D, Xp, Din, t, Din, beta=1.0), dy, Xp):
-                t = _grad_target(w)
-                dw = _empty((D, Din), Xp) if t is None else None
-                gemm("M", "N", D, Din, rows, dy, D, Xp, Din, dw if t is None else t, Din, beta=0.0 if t is None else 1.0)
-            grads.append(dw)
+        dgamma, dbeta, dbk, dbv = _kv_norm_backward(dKn, dV, Khat, rstd, gamma, *ctx.biases)
+        grads = [deliver_wgrad(w, lambda t, beta, dy=dy: gemm("M", "N", D, Din, rows, dy, D, Xp, Din, t, Din, beta=beta), (D, Din), dy, Xp)
+                 for w, dy in ((wk, dKn), (wv, dV))]      # dW = dy^T Xp
         dX = _empty((rows, Din), Xp)
         gemm("K", "N", rows, Din, D, dKn, D, wk, Din, dX, Din)
         gemm("K", "N", rows, Din, D, dV, D, wv, Din, dX, Din, beta=1.0)

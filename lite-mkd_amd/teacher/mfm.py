@@ -20,22 +20,14 @@ from .. import ops
 from .._lib import lib
 
 
-def _s():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _p(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
 def layernorm(x, gamma, beta, res=None, res_rows=0, out=None, ldy=None, col_off=0):
     rows, D = x.shape
     if out is None:
         out = torch.empty_like(x)
         ldy = D
     ops._chk(x, gamma, beta, res)
-    y_ptr = ctypes.c_void_p(out.data_ptr() + 4 * col_off)
-    lib().call("lmkd_layernorm_fwd", _p(x), _p(res), res_rows, _p(gamma), _p(beta), y_ptr, ldy, rows, D, ctypes.c_float(1e-5), _s())
+    lib().call("lmkd_layernorm_fwd", ops._p(x), ops._p(res), res_rows, ops._p(gamma), ops._p(beta), ctypes.c_void_p(ops._pw(out) + 4 * col_off), ldy,
+               rows, D, ops._f32(1e-5), ops._stream())
     return out
 
 
@@ -62,7 +54,7 @@ def _encoder_layer(x, layer, L, nhead):
     # library's default arithmetic, the fp32 MFMA GEMM in the native mode
     qkv = ops.linear_infer(x, at.in_proj_weight, at.in_proj_bias)
     ctx = torch.empty_like(x)
-    lib().call("lmkd_mha_small", _p(qkv), _p(ctx), M // L, L, D, nhead, _s())
+    lib().call("lmkd_mha_small", ops._p(qkv), ops._p(ctx), M // L, L, D, nhead, ops._stream())
     o = ops.linear_infer(ctx, at.out_proj.weight, at.out_proj.bias)
     x = layernorm(x, layer.norm1.weight, layer.norm1.bias, o, M)
     h = ops.linear_infer(x, layer.linear1.weight, layer.linear1.bias, relu=True)
@@ -216,5 +208,5 @@ class ThreeTRXShiftLoopTime(nn.Module):
         f2 = self.fusion.extract_feature(rgb, torch.cat((depth[:, s:], depth[:, :s]), dim=1).contiguous())
         f3 = self.fusion.extract_feature(rgb, torch.cat((flow[:, s:], flow[:, :s]), dim=1).contiguous())
         for f in (f2, f3):
-            lib().call("lmkd_axpby", _p(f), _p(out), ctypes.c_float(1.0), ctypes.c_float(1.0), out.numel(), _s())
+            lib().call("lmkd_axpby", ops._p(f), ops._p(out), ops._f32(1.0), ops._f32(1.0), out.numel(), ops._stream())
         return out

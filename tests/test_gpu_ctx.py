@@ -159,6 +159,34 @@ def test_every_output_element_is_written(dev, case):
     assert torch.equal(out["g_support"].reshape(Ns * L, Din), dX[:Ns * L].cpu()) and torch.equal(out["g_query"].reshape(Nq * L, Din), dX[Ns * L:].cpu())
 
 
+# (rows, D): most lanes idle; D no multiple of the 256 lanes; 24 elements per lane; the head's own width
+@pytest.mark.parametrize("shape", [(5, 64), (6, 300), (4, 6144), (7, 1152)], ids=lambda s: "r%dD%d" % s)
+def test_key_layernorm_equals_the_training_layernorm_bit_for_bit(dev, shape):
+    """lmkd_ctx_ln_fwd against lmkd_layernorm_train_fwd without residual and mask; in place against out of place; without Khat and rstd"""
+    import litemkd_amd
+    from litemkd_amd import ops
+    lib, p, st = litemkd_amd.lib(), ops._p, ops._stream()
+    rows, D = shape
+    g = torch.Generator().manual_seed(4000 + rows + D)
+    Kraw, gamma, beta = torch.randn(rows, D, generator=g).to(dev), (1 + 0.1 * torch.randn(D, generator=g)).to(dev), (0.1 * torch.randn(D, generator=g)).to(dev)
+    nan = lambda *s: torch.full(s, float("nan"), device=dev)      # noqa: E731
+    eps = ops._f32(1e-5)
+    Kn, Khat, rstd = nan(rows, D), nan(rows, D), nan(rows)
+    lib.call("lmkd_ctx_ln_fwd", p(Kraw), p(gamma), p(beta), p(Kn), p(Khat), p(rstd), rows, D, eps, st)
+    y, xhat, rs = nan(rows, D), nan(rows, D), nan(rows)
+    lib.call("lmkd_layernorm_train_fwd", p(Kraw), None, 0, p(gamma), p(beta), None, p(y), D, p(xhat), p(rs), rows, D, eps, st)
+    Kin, Khat_in, rstd_in = Kraw.clone(), nan(rows, D), nan(rows)
+    lib.call("lmkd_ctx_ln_fwd", p(Kin), p(gamma), p(beta), p(Kin), p(Khat_in), p(rstd_in), rows, D, eps, st)
+    Kbare = nan(rows, D)
+    lib.call("lmkd_ctx_ln_fwd", p(Kraw), p(gamma), p(beta), p(Kbare), None, None, rows, D, eps, st)
+    torch.cuda.synchronize()
+    for t in (Kn, Khat, rstd):
+        assert bool(torch.isfinite(t).all())
+    assert torch.equal(Kn, y) and torch.equal(Khat, xhat) and torch.equal(rstd, rs)
+    assert torch.equal(Kin, Kn) and torch.equal(Khat_in, Khat) and torch.equal(rstd_in, rstd)
+    assert torch.equal(Kbare, Kn)
+
+
 def test_dropout_mask_is_applied_forward_and_backward(dev):
     from litemkd_amd import ops
     case = 1

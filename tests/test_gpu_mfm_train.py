@@ -186,6 +186,51 @@ def test_layernorm_kernels_are_anchored_to_fp64(dev, shape, masked):
         assert torch.equal(y.cpu(), a["y"])
 
 
+# entry points that state the same arithmetic must agree to the bit.  (rows, D, res_rows): most lanes idle; D no multiple of the 256
+# lanes and 6 % 3 wrapping the residual rows; 24 elements per lane; no residual
+LN_EQ_CASES = [(5, 64, 5), (6, 300, 3), (4, 6144, 4), (6, 300, None)]
+
+
+@pytest.mark.parametrize("case", LN_EQ_CASES, ids=lambda c: "r%dD%dres%s" % c)
+def test_inference_and_training_layernorm_forward_are_bit_equal(dev, case):
+    import ctypes
+    import litemkd_amd
+    from litemkd_amd import ops
+    lib, p, st = litemkd_amd.lib(), ops._p, ops._stream()
+    rows, D, rr = case
+    g = torch.Generator().manual_seed(3000 + rows + D)
+    x, gamma, beta = torch.randn(rows, D, generator=g).to(dev), (1 + 0.1 * torch.randn(D, generator=g)).to(dev), (0.1 * torch.randn(D, generator=g)).to(dev)
+    res = torch.randn(rr, D, generator=g).to(dev) if rr else None
+    ld, off = 2 * D + 4, D + 4
+    wi, wt, xhat, rstd = _nan(dev, rows, ld), _nan(dev, rows, ld), _nan(dev, rows, D), _nan(dev, rows)
+    lib.call("lmkd_layernorm_fwd", p(x), p(res), rr or 0, p(gamma), p(beta), ctypes.c_void_p(wi.data_ptr() + 4 * off), ld, rows, D,
+             ops._f32(R.EPS), st)
+    lib.call("lmkd_layernorm_train_fwd", p(x), p(res), rr or 0, p(gamma), p(beta), None, ctypes.c_void_p(wt.data_ptr() + 4 * off), ld, p(xhat),
+             p(rstd), rows, D, ops._f32(R.EPS), st)
+    torch.cuda.synchronize()
+    for w in (wi, wt):
+        assert bool(torch.isnan(torch.cat([w[:, :off].reshape(-1), w[:, off + D:].reshape(-1)])).all()), "wrote outside its column slice"
+        assert bool(torch.isfinite(w[:, off:off + D]).all())
+    assert torch.equal(wi[:, off:off + D], wt[:, off:off + D])
+
+
+@pytest.mark.parametrize("shape", [c[:2] for c in LN_EQ_CASES[:3]], ids=lambda s: "r%dD%d" % s)
+def test_in_place_and_training_layernorm_backward_are_bit_equal(dev, shape):
+    import litemkd_amd
+    from litemkd_amd import ops
+    lib, p, st = litemkd_amd.lib(), ops._p, ops._stream()
+    rows, D = shape
+    g = torch.Generator().manual_seed(3100 + rows + D)
+    dy, xhat, gamma = torch.randn(rows, D, generator=g).to(dev), torch.randn(rows, D, generator=g).to(dev), (1 + 0.1 * torch.randn(D, generator=g)).to(dev)
+    rstd = (0.5 + torch.rand(rows, generator=g)).to(dev)
+    dK, dpre = dy.clone(), _nan(dev, rows, D)
+    lib.call("lmkd_layernorm_bwd_rows", p(dK), p(xhat), p(rstd), p(gamma), rows, D, st)
+    lib.call("lmkd_layernorm_train_bwd", p(dy), D, None, p(xhat), p(rstd), p(gamma), p(dpre), None, rows, D, st)
+    torch.cuda.synchronize()
+    assert bool(torch.isfinite(dpre).all()) and not torch.equal(dK, dy)
+    assert torch.equal(dK, dpre)
+
+
 # ---------------------------------------------------------------------------------------------------------------------------------
 # the fusions
 # ---------------------------------------------------------------------------------------------------------------------------------
