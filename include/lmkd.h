@@ -120,19 +120,17 @@ long lmkd_conv_h2_fallbacks(void); /* mode-4 launches that carried LMKD_AMAX_FEN
    maximum starts lmkd_amax_words() / 2 words in): a pass of its own, for tensors no kernel of this library wrote */
 int lmkd_amax(const float* x, long n, void* word, void* stream);
 long lmkd_amax_words(void);
-/* 16-bit elements of the plane buffer lmkd_conv2d_split_weights fills for a packed weight [ncols][Kp] in the current mode:
-   ncols Kp (mode 1), 12 ncols Kp (2 / 3), 18 ncols Kp + 32 (4: + the two fp16 planes of W and of -W in the 16x16x32 order, 64 bytes
-   holding max |w|, and the two fp16 planes of W in the 32x32x16 order) */
+/* 16-bit elements of the plane buffer lmkd_conv2d_split_weights fills for a packed weight [ncols][Kp] in the current mode; its layout:
+   DESIGN.md 3.1 (csrc/wplanes.h) */
 long lmkd_conv2d_plane_elems(int ncols, int Kp);
 long lmkd_conv_h2_launches(void); /* launches that took the two-plane form so far (tests) */
-/* re-pack n convolution weights in ONE launch (after an optimizer step; trainwandb.py:142): entry i = OIHW weight ws[i] -> wfs[i], the
+/* re-pack n convolution weights in ONE launch per pass (after an optimizer step; trainwandb.py:142): entry i = OIHW weight ws[i] -> wfs[i], the
    buffer lmkd_conv2d_pack_weights + lmkd_conv2d_split_weights would fill for dims[6 i ..] = (Cout, Cin, Cs, KH, KW, mode), bit for bit.
    Modes 1-4 of lmkd_conv_set_compute_dtype.  The pointer / dims arrays are host memory. */
 int lmkd_conv2d_repack_multi(const float* const* ws, void* const* wfs, const int* dims, int n, void* stream);
 /* wp: fp32 K-major packed weights [ncols][Kp] (lmkd_conv2d_pack_weights; ncols = Cout forward, Cin data gradient)
-   -> wf: bf16 in MFMA fragment order: mode 1: ncols * Kp (one round-to-nearest plane); modes 2/3: 12 * ncols * Kp = the three planes
-   of W and the three planes of -W (half the row tiles accumulate -y, csrc/conv_x3.h X3FragB) in the v_mfma 32x32x16 fragment order,
-   then the same six planes in the 16x16x32 order (csrc/conv_patch16.h) */
+   -> wf: the weight's plane buffer of lmkd_conv2d_plane_elems(ncols, Kp) 16-bit elements in the current mode (1 - 4): 16-bit planes in
+   MFMA fragment order, laid out as DESIGN.md 3.1 says (csrc/wplanes.h); ncols and Kp multiples of 32 */
 int lmkd_conv2d_split_weights(const float* wp, void* wf, int ncols, int Kp, void* stream);
 int lmkd_conv_get_compute_dtype(void);
 int lmkd_conv_set_wgrad_planes(int on); /* tuning (modes 1-3): 1 = weight gradient on the bf16-plane kernel with transposed LDS reads (default), 0 = fp32-tile kernel */

@@ -362,8 +362,8 @@ __global__ __launch_bounds__(Cfg::THREADS) void conv_gemm_kernel(ConvGemmArgs a)
   }
 }
 
+#include "wplanes.h"
 #include "conv_x3.h"
-#include "h2.h"
 #include "conv_patch.h"
 #include "conv_patch16.h"
 #include "conv_stem.h"
@@ -593,31 +593,12 @@ static void launch_wgrad_reduce(const float* slab, float* dw, int splits, int Co
 #include "wgrad_win.h"
 #include "wgrad_stem.h"
 
-// K-major packed weights (the GEMM's B operand: one row of K per output column):
-// mode 0 (forward): Wp[co][(kh*KWp+kw)*Cs + ci] = W[co][ci][kh][kw]   (zero for padded kw / ci)
-// mode 1 (dgrad)  : Wd[ci][(kh*KW+kw)*Co + co] = W[co][ci][kh][kw]
-__global__ void pack_weights_kernel(const float* __restrict__ w, float* __restrict__ wp, int Co, int Cin, int Cs, int KH,
-                                    int KW, int KWp, int mode) {
-  if (mode == 0) {
-    const long total = (long)Co * KH * KWp * Cs;
-    for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
-      const int ci = idx % Cs;
-      long r = idx / Cs;
-      const int kw = r % KWp; r /= KWp;
-      const int kh = r % KH;
-      const int co = r / KH;
-      wp[idx] = (ci < Cin && kw < KW) ? w[(((long)co * Cin + ci) * KH + kh) * KW + kw] : 0.f;
-    }
-  } else {
-    const long total = (long)Cin * KH * KW * Co;
-    for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
-      const int co = idx % Co;
-      long r = idx / Co;
-      const int kw = r % KW; r /= KW;
-      const int kh = r % KH;
-      const int ci = r / KH;
-      wp[idx] = w[(((long)co * Cin + ci) * KH + kh) * KW + kw];
-    }
+// K-major packed weights (the GEMM's B operand: one row of K per output column) in the pack order of wplanes.h (WplOihw)
+__global__ void pack_weights_kernel(WplOihw e, float* __restrict__ wp) {
+  const long total = (long)e.ncols * e.Kp;
+  for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
+    const int col = (int)(idx / e.Kp);
+    wp[idx] = e.fetch(col, (int)(idx - (long)col * e.Kp));
   }
 }
 
@@ -627,9 +608,15 @@ __global__ void pack_weights_kernel(const float* __restrict__ w, float* __restri
 static inline int conv_out(int H, int K, int s, int p) { return (H + 2 * p - K) / s + 1; }
 static inline int kw_padded(int Cs, int KW) { return Cs >= 32 ? KW : ((KW * Cs + 31) / 32) * 32 / Cs; }
 
+// the source of a weight's packed elements: dims as the entry points take them; ncols x Kp is the packed weight
+static WplOihw wpl_oihw(const float* w, void* wf, int Cout, int Cin, int Cs, int KH, int KW, int mode) {
+  const int KWp = kw_padded(Cs, KW);
+  return WplOihw{w, (unsigned short*)wf, Cout, Cin, Cs, KH, KW, KWp, mode, mode == 0 ? Cout : Cin, mode == 0 ? KH * KWp * Cs : KH * KW * Cout};
+}
+
 extern "C" long lmkd_conv2d_packed_weight_elems(int Cout, int Cin, int Cs, int KH, int KW, int mode) {
-  if (mode == 0) return (long)Cout * KH * kw_padded(Cs, KW) * Cs;
-  return (long)Cin * KH * KW * Cout;
+  const WplOihw e = wpl_oihw(nullptr, nullptr, Cout, Cin, Cs, KH, KW, mode);
+  return (long)e.ncols * e.Kp;
 }
 
 extern "C" int lmkd_conv2d_pack_weights(const float* w_oihw, float* wp, int Cout, int Cin, int Cs, int KH, int KW,
@@ -637,11 +624,10 @@ extern "C" int lmkd_conv2d_pack_weights(const float* w_oihw, float* wp, int Cout
   LMKD_REQUIRE(w_oihw && wp, "lmkd_conv2d_pack_weights: null pointer");
   LMKD_REQUIRE(mode == 0 || mode == 1, "lmkd_conv2d_pack_weights: mode must be 0 (fwd) or 1 (dgrad)");
   LMKD_REQUIRE(Cs >= Cin && (Cs % 32 == 0 || Cs == 4), "lmkd_conv2d_pack_weights: Cs=%d must be 4 or a multiple of 32", Cs);
-  const long total = lmkd_conv2d_packed_weight_elems(Cout, Cin, Cs, KH, KW, mode);
-  int grid = cdiv(total, 256);
+  const WplOihw e = wpl_oihw(w_oihw, nullptr, Cout, Cin, Cs, KH, KW, mode);
+  int grid = cdiv((long)e.ncols * e.Kp, 256);
   if (grid > 4096) grid = 4096;
-  hipLaunchKernelGGL(pack_weights_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, w_oihw, wp, Cout, Cin, Cs, KH, KW,
-                     kw_padded(Cs, KW), mode);
+  hipLaunchKernelGGL(pack_weights_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, e, wp);
   LMKD_CHECK_LAUNCH("lmkd_conv2d_pack_weights");
   return LMKD_OK;
 }
@@ -685,183 +671,78 @@ static inline void note_fenced(const lmkd_amax_desc* am) { if (conv_h2() && am &
 // them.  out_words (forward): the launch also folds max |y| into these words - in the epilogue of conv_patch16_x3_kernel, or by a
 // reduction pass of its own behind any other kernel - so that lmkd_bn_finalize_seg can bound relu(BatchNorm(y)) for a consumer that
 // applies the BatchNorm in its loader.
-// elements (16-bit) of the plane buffer of a packed weight of ncols x Kp in the current mode
-extern "C" long lmkd_conv2d_plane_elems(int ncols, int Kp) {
-  const long n = (long)ncols * Kp;
-  return conv_nprod() == 1 ? n : (conv_h2() ? 18 * n + 32 : 12 * n);
-}
-// max |x| of n floats: slots = 0: into the ONE word at `word` (weight packs); slots = 1: into the slot words of one frame segment of an
-// activation maximum (lmkd_amax_next's layout: segment s at word + s * lmkd_amax_words() / 2).  The words are zeroed here first.
-static int amax_impl(const float* x, long n, void* word, int slots, void* stream, bool zero = true) {
+// elements (16-bit) of the plane buffer of a packed weight of ncols x Kp in the current mode (wplanes.h)
+extern "C" long lmkd_conv2d_plane_elems(int ncols, int Kp) { return wpl_total((long)ncols * Kp, g_conv_mode); }
+// max |x| of n floats into the slot words of one frame segment of an activation maximum (lmkd_amax_next's layout: segment s at
+// word + s * lmkd_amax_words() / 2).  The words are zeroed here first (zero).
+static int amax_impl(const float* x, long n, void* word, void* stream, bool zero = true) {
   LMKD_REQUIRE(x && word && n > 0, "lmkd_amax: bad arguments");
-  if (zero && hipMemsetAsync(word, 0, slots ? LMKD_AMAX_SEG_WORDS * 4 : 4, (hipStream_t)stream) != hipSuccess) {
+  if (zero && hipMemsetAsync(word, 0, LMKD_AMAX_SEG_WORDS * 4, (hipStream_t)stream) != hipSuccess) {
     lmkd_set_error("lmkd_amax: hipMemsetAsync failed");
     return LMKD_EHIP;
   }
   int grid = cdiv(n, 256 * 16);
   if (grid > 2048) grid = 2048;
-  if (slots) hipLaunchKernelGGL(amax_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, n, (unsigned*)word);
-  else hipLaunchKernelGGL(amax_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, n, (unsigned*)word);
+  hipLaunchKernelGGL(amax_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, n, (unsigned*)word);
   LMKD_CHECK_LAUNCH("amax_kernel");
   return LMKD_OK;
 }
-extern "C" int lmkd_amax(const float* x, long n, void* word, void* stream) { return amax_impl(x, n, word, 1, stream); }
+extern "C" int lmkd_amax(const float* x, long n, void* word, void* stream) { return amax_impl(x, n, word, stream); }
 
-extern "C" int lmkd_conv2d_split_weights(const float* wp, void* wf, int ncols, int Kp, void* stream) {
-  LMKD_REQUIRE(wp && wf, "lmkd_conv2d_split_weights: null pointer");
-  LMKD_REQUIRE(ncols > 0 && ncols % 32 == 0 && Kp > 0 && Kp % 32 == 0, "lmkd_conv2d_split_weights: ncols=%d and Kp=%d must be multiples of 32", ncols, Kp);
-  LMKD_REQUIRE((long)ncols * Kp * 24 < 0xffffffe0L, "lmkd_conv2d_split_weights: weights exceed the 4 GiB buffer range");
-  int grid = cdiv((long)ncols * Kp, 256);
-  if (grid > 4096) grid = 4096;
-  hipLaunchKernelGGL(split_weights_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, wp, (unsigned short*)wf, ncols, Kp,
-                     conv_nprod() == 1 ? 1 : 3);
-  LMKD_CHECK_LAUNCH("split_weights_kernel");
-  if (conv_nprod() != 1) {      // three-plane modes: the 16x16x32 fragment order behind the two 32x32x16 copies (conv_patch16.h)
-    hipLaunchKernelGGL(split_weights16_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, wp, (unsigned short*)wf + (long)ncols * Kp * 6, ncols, Kp);
-    LMKD_CHECK_LAUNCH("split_weights16_kernel");
+// The plane buffers of the m entries of a batch in the current arithmetic (modes 1 - 4; wplanes.h): gx workgroups per entry and pass
+template <class E, int N>
+static int wpl_write(WplBatch<E, N>& a, int m, int gx, void* stream) {
+  using B = WplBatch<E, N>;
+  a.npl = conv_nprod() == 1 ? 1 : 3;
+  a.h2 = conv_h2();
+  for (int j = 0; j < m; ++j) {
+    const E& e = a.e[j];
+    LMKD_REQUIRE(e.ncols > 0 && e.ncols % 32 == 0 && e.Kp > 0 && e.Kp % 32 == 0, "weight planes: entry %d: ncols=%d and Kp=%d must be multiples of 32", j, e.ncols, e.Kp);
+    LMKD_REQUIRE(2 * wpl_total((long)e.ncols * e.Kp, 2) < 0xffffffe0L, "weight planes: entry %d: weights exceed the 4 GiB buffer range", j);
   }
-  if (conv_h2()) {         // + the two fp16 planes (16x16x32 order) and max |w| behind them
-    unsigned short* wh = (unsigned short*)wf + (long)ncols * Kp * 12;
-    const int rc = amax_impl(wp, (long)ncols * Kp, wh + (long)ncols * Kp * 4, 0, stream);
-    if (rc) return rc;
-    hipLaunchKernelGGL(split_weights16_h2_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, wp, wh, ncols, Kp);
-    LMKD_CHECK_LAUNCH("split_weights16_h2_kernel");
-    hipLaunchKernelGGL(split_weights_h2_32_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, wp, wh, ncols, Kp);
-    LMKD_CHECK_LAUNCH("split_weights_h2_32_kernel");
+  hipLaunchKernelGGL(wpl_bf16_kernel<B>, dim3(gx, m), dim3(256), 0, (hipStream_t)stream, a);
+  LMKD_CHECK_LAUNCH("wpl_bf16_kernel");
+  if (a.h2) {
+    hipLaunchKernelGGL(wpl_amax_kernel<B>, dim3(std::min(gx, 512), m), dim3(256), 0, (hipStream_t)stream, a);      // (one atomic per wave on the entry's word: few workgroups)
+    LMKD_CHECK_LAUNCH("wpl_amax_kernel");
+    hipLaunchKernelGGL(wpl_h2_kernel<B>, dim3(gx, m), dim3(256), 0, (hipStream_t)stream, a);
+    LMKD_CHECK_LAUNCH("wpl_h2_kernel");
   }
   return LMKD_OK;
 }
 
-// Re-pack MANY convolution weights in one launch (after an optimizer step: 40 cached packs = 120 pack / split launches before).
-// Entry e: OIHW weight -> the fragment-order planes lmkd_conv2d_pack_weights + lmkd_conv2d_split_weights would write for (Cs, mode) in
-// the current arithmetic (modes 1-3), bit for bit; blockIdx.y = entry.
-struct RepackEntry {
-  const float* w;
-  unsigned short* wf;
-  int Co, Cin, Cs, KH, KW, KWp, mode, ncols, Kp;
-};
-#define LMKD_REPACK_MAX 40
-struct RepackArgs {
-  RepackEntry e[LMKD_REPACK_MAX];
-  int npl;
-};
-// element (col, k) of the packed weight of entry e (pack_weights_kernel)
-__device__ __forceinline__ float repack_fetch(const RepackEntry& e, int col, int k) {
-  if (e.mode == 0) {      // mode 0: col = co, k = (kh * KWp + kw) * Cs + ci
-    const int ci = k % e.Cs;
-    const int r = k / e.Cs;
-    const int kw = r % e.KWp, kh = r / e.KWp;
-    return (ci < e.Cin && kw < e.KW) ? e.w[(((long)col * e.Cin + ci) * e.KH + kh) * e.KW + kw] : 0.f;
-  }
-  // mode 1: col = ci, k = (kh * KW + kw) * Co + co
-  const int co = k % e.Co;
-  const int r = k / e.Co;
-  const int kw = r % e.KW, kh = r / e.KW;
-  return e.w[(((long)co * e.Cin + col) * e.KH + kh) * e.KW + kw];
-}
-// mode 4: the fp16 planes behind the bf16 ones, in three launches: phase 0 zeroes the entries' max |w| words, 1 folds the maxima, 2 splits
-__global__ void repack_h2_kernel(RepackArgs a, int phase) {
-  const RepackEntry& e = a.e[blockIdx.y];
-  const long total = (long)e.ncols * e.Kp;
-  unsigned short* wh = e.wf + total * 12;
-  unsigned* word = reinterpret_cast<unsigned*>(wh + total * 4);
-  if (phase == 0) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) *word = 0u;
-    return;
-  }
-  if (phase == 1) {
-    float m = 0.f;
-    for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
-      const int col = (int)(idx / e.Kp), k = (int)(idx - (long)col * e.Kp);
-      m = fmaxf(m, fabsf(repack_fetch(e, col, k)));
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-    if ((threadIdx.x & 63) == 0) atomicMax(word, __float_as_uint(m));
-    return;
-  }
-  const float s = h2_scale(*word);
-  const int G16 = e.Kp >> 5, G = e.Kp >> 4;
-  unsigned short* wh32 = wh + total * 4 + 32;      // split_weights_h2_32_kernel
-  for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
-    const int col = (int)(idx / e.Kp), k = (int)(idx - (long)col * e.Kp);
-    const int lane16 = (col & 15) + 16 * patch16_kslot((k >> 3) & 3);
-    const long q = ((((long)(col >> 4) * G16 + (k >> 5)) * 2) * 64 + lane16) * 8 + (k & 7);
-    unsigned short p0, p1;
-    h2_split1(repack_fetch(e, col, k) * s, p0, p1);
-    wh[q] = p0; wh[q + 512] = p1;
-    const long q2 = q + total * 2;
-    wh[q2] = p0 ^ 0x8000u; wh[q2 + 512] = p1 ^ 0x8000u;
-    const long o = ((((long)(col >> 5) * G + (k >> 4)) * 2) * 64 + (col & 31) + 32 * ((k >> 3) & 1)) * 8 + (k & 7);
-    wh32[o] = p0; wh32[o + 512] = p1;
-  }
-}
-__global__ void repack_multi_kernel(RepackArgs a) {
-  const RepackEntry& e = a.e[blockIdx.y];
-  const long total = (long)e.ncols * e.Kp;
-  const int G = e.Kp >> 4, G16 = e.Kp >> 5;
-  for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
-    const int col = (int)(idx / e.Kp), k = (int)(idx - (long)col * e.Kp);
-    const float x = repack_fetch(e, col, k);
-    const int lane = (col & 31) + 32 * ((k >> 3) & 1);
-    const long o = ((((long)(col >> 5) * G + (k >> 4)) * a.npl) * 64 + lane) * 8 + (k & 7);
-    if (a.npl == 1) {
-      union { __bf16 h; unsigned short u; } c;
-      c.h = (__bf16)x;
-      e.wf[o] = c.u;
-      continue;
-    }
-    const unsigned b0 = __float_as_uint(x);
-    const float r1 = x - __uint_as_float(b0 & 0xffff0000u);
-    const unsigned b1 = __float_as_uint(r1);
-    const float r2 = r1 - __uint_as_float(b1 & 0xffff0000u);
-    const unsigned short p0 = (unsigned short)(b0 >> 16), p1 = (unsigned short)(b1 >> 16), p2 = (unsigned short)(__float_as_uint(r2) >> 16);
-    const unsigned short n0 = p0 ^ 0x8000u, n1 = p1 ^ 0x8000u, n2 = p2 ^ 0x8000u;
-    e.wf[o] = p0; e.wf[o + 512] = p1; e.wf[o + 1024] = p2;                        // split_weights_kernel: W, then -W
-    const long o2 = o + total * 3;
-    e.wf[o2] = n0; e.wf[o2 + 512] = n1; e.wf[o2 + 1024] = n2;
-    unsigned short* w16 = e.wf + total * 6;                                         // split_weights16_kernel behind them
-    const int lane16 = (col & 15) + 16 * patch16_kslot((k >> 3) & 3);
-    const long q = ((((long)(col >> 4) * G16 + (k >> 5)) * 3) * 64 + lane16) * 8 + (k & 7);
-    w16[q] = p0; w16[q + 512] = p1; w16[q + 1024] = p2;
-    const long q2 = q + total * 3;
-    w16[q2] = n0; w16[q2 + 512] = n1; w16[q2 + 1024] = n2;
-  }
+extern "C" int lmkd_conv2d_split_weights(const float* wp, void* wf, int ncols, int Kp, void* stream) {
+  LMKD_REQUIRE(wp && wf, "lmkd_conv2d_split_weights: null pointer");
+  WplBatch<WplPacked, 1> a;
+  a.e[0] = WplPacked{wp, (unsigned short*)wf, ncols, Kp};
+  int grid = cdiv((long)ncols * Kp, 256);
+  if (grid > 4096) grid = 4096;
+  return wpl_write(a, 1, grid, stream);
 }
 
-// ws[i], wfs[i]: OIHW weight and destination planes of entry i; dims[i * 6 ..] = Cout, Cin, Cs, KH, KW, mode.  Modes 1-3 only.
+// Re-pack MANY convolution weights in one launch per pass (after an optimizer step: 40 cached packs = 120 pack / split launches before).
+// ws[i], wfs[i]: OIHW weight and destination planes of entry i; dims[i * 6 ..] = Cout, Cin, Cs, KH, KW, mode: what
+// lmkd_conv2d_pack_weights + lmkd_conv2d_split_weights would write in the current arithmetic (modes 1 - 4), bit for bit.
+#define LMKD_REPACK_MAX 40
 extern "C" int lmkd_conv2d_repack_multi(const float* const* ws, void* const* wfs, const int* dims, int n, void* stream) {
   LMKD_REQUIRE(ws && wfs && dims && n > 0, "lmkd_conv2d_repack_multi: null pointer");
   LMKD_REQUIRE(conv_planes(), "lmkd_conv2d_repack_multi: fragment-order planes exist in the bf16-plane modes only");
   for (int i0 = 0; i0 < n; i0 += LMKD_REPACK_MAX) {
-    RepackArgs a;
+    WplBatch<WplOihw, LMKD_REPACK_MAX> a;
     memset(&a, 0, sizeof(a));
-    a.npl = conv_nprod() == 1 ? 1 : 3;
     const int m = std::min(LMKD_REPACK_MAX, n - i0);
     long most = 0;
     for (int j = 0; j < m; ++j) {
       const int* d = dims + (long)(i0 + j) * 6;
-      RepackEntry& e = a.e[j];
-      e.w = ws[i0 + j]; e.wf = (unsigned short*)wfs[i0 + j];
-      e.Co = d[0]; e.Cin = d[1]; e.Cs = d[2]; e.KH = d[3]; e.KW = d[4]; e.mode = d[5];
-      LMKD_REQUIRE(e.w && e.wf && (e.mode == 0 || e.mode == 1), "lmkd_conv2d_repack_multi: bad entry %d", i0 + j);
-      LMKD_REQUIRE(e.Cs >= e.Cin && (e.Cs % 32 == 0 || e.Cs == 4), "lmkd_conv2d_repack_multi: Cs=%d must be 4 or a multiple of 32", e.Cs);
-      e.KWp = kw_padded(e.Cs, e.KW);
-      e.ncols = e.mode == 0 ? e.Co : e.Cin;
-      e.Kp = e.mode == 0 ? e.KH * e.KWp * e.Cs : e.KH * e.KW * e.Co;
-      LMKD_REQUIRE(e.ncols % 32 == 0 && e.Kp % 32 == 0, "lmkd_conv2d_repack_multi: entry %d: ncols=%d and Kp=%d must be multiples of 32", i0 + j, e.ncols, e.Kp);
-      most = std::max(most, (long)e.ncols * e.Kp);
+      LMKD_REQUIRE(ws[i0 + j] && wfs[i0 + j] && (d[5] == 0 || d[5] == 1), "lmkd_conv2d_repack_multi: bad entry %d", i0 + j);
+      LMKD_REQUIRE(d[2] >= d[1] && (d[2] % 32 == 0 || d[2] == 4), "lmkd_conv2d_repack_multi: Cs=%d must be 4 or a multiple of 32", d[2]);
+      a.e[j] = wpl_oihw(ws[i0 + j], wfs[i0 + j], d[0], d[1], d[2], d[3], d[4], d[5]);
+      most = std::max(most, (long)a.e[j].ncols * a.e[j].Kp);
     }
     int gx = cdiv(most, 256 * 4);
     if (gx > 512) gx = 512;
-    hipLaunchKernelGGL(repack_multi_kernel, dim3(gx, m), dim3(256), 0, (hipStream_t)stream, a);
-    LMKD_CHECK_LAUNCH("repack_multi_kernel");
-    if (conv_h2()) {
-      for (int phase = 0; phase < 3; ++phase) {
-        hipLaunchKernelGGL(repack_h2_kernel, dim3(phase == 0 ? 1 : gx, m), dim3(256), 0, (hipStream_t)stream, a, phase);
-        LMKD_CHECK_LAUNCH("repack_h2_kernel");
-      }
-    }
+    const int rc = wpl_write(a, m, gx, stream);
+    if (rc) return rc;
   }
   return LMKD_OK;
 }
@@ -1482,8 +1363,8 @@ static int conv2d_fwd_impl(const float* x, const float* wp, float* y, float* sta
     // lmkd_conv_output_amax on a launch whose kernel does not fold the maximum in its epilogue: a reduction pass of its own per frame
     // segment (rare shapes; the trunk's 3x3 convolutions all run conv_patch16_x3_kernel) - the words are never left at "unknown"
     const long per = (long)Ho * Wo * Cout, n0 = seg_n0 ? seg_n0 * per : (long)N * per;
-    rc = amax_impl(y, n0, a.amax_out, 1, stream, false);
-    if (rc == LMKD_OK && seg_n0) rc = amax_impl(y + n0, (long)N * per - n0, a.amax_out + LMKD_AMAX_SEG_WORDS, 1, stream, false);
+    rc = amax_impl(y, n0, a.amax_out, stream, false);
+    if (rc == LMKD_OK && seg_n0) rc = amax_impl(y + n0, (long)N * per - n0, a.amax_out + LMKD_AMAX_SEG_WORDS, stream, false);
   }
   return rc;
 }

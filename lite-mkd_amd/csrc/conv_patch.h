@@ -281,14 +281,11 @@ __global__ __launch_bounds__(Cfg::THREADS, Cfg::MINW) void conv_patch_x3_kernel(
     unsigned h2_xbits = 0u, h2_wbits = 0u;      // (loads in flight; reduced below)
     if constexpr (NPROD == 3) {
       h2_xbits = a.h2_xw[cur.seg * LMKD_AMAX_SEG_WORDS + (tid & (LMKD_AMAX_SLOTS - 1)) * LMKD_AMAX_STRIDE];
-      h2_wbits = *reinterpret_cast<const unsigned*>(reinterpret_cast<const unsigned short*>(a.wpk) + (long)a.Co * a.Kp * 16);
+      h2_wbits = *reinterpret_cast<const unsigned*>(reinterpret_cast<const unsigned short*>(a.wpk) + wpl_amax((long)a.Co * a.Kp));
     }
     LB lb;
     const bool neg = NPL == 3 && NPROD != 3 && x3_neg_tile(cur.ltile, cur.ltiles);      // half the row tiles (of the segment) accumulate -y: X3FragB::init
-    if constexpr (NPROD == 3)      // the fp16 planes of W in the 32x32x16 order: behind the bf16 planes, the 16x16x32 fp16 planes and the maximum's 64 bytes
-      lb.init(reinterpret_cast<const unsigned short*>(a.wpk) + (long)a.Co * a.Kp * 16 + 32, a.Co, a.Kp, n0 + wn * (Cfg::TN * 32), lane, false);
-    else
-      lb.init(a.wpk, a.Co, a.Kp, n0 + wn * (Cfg::TN * 32), lane, neg);
+    lb.init(a.wpk, a.Co, a.Kp, n0 + wn * (Cfg::TN * 32), lane, neg);      // (NPROD == 3: the fp16 planes in the 32x32x16 order, which have no -W copy)
     u32x4 rb0[LB::NR], rb1[LB::NR];
     int b_tp = 0, b_cc = 0;      // (tap, chunk) of the next B fragments to fetch
     // the weight fragments of the first two K-steps go out before the tables are written: their K offsets come from the tap lanes

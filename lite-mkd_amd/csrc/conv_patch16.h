@@ -26,7 +26,7 @@
 #define LMKD_ABL 0
 #endif
 
-__device__ __host__ __forceinline__ constexpr int patch16_kslot(int q) { return ((q & 1) << 1) | (q >> 1); }      // self-inverse
+// (patch16_kslot, the k-slot permutation: wplanes.h - it is part of the weights' 16x16x32 fragment order)
 __device__ __forceinline__ int patch16_pixel(int j) { return (j >= 4 && j < 12) ? 2 * (j - 4) : (j < 4 ? 2 * j + 1 : 2 * (j - 8) + 1); }
 
 // v + (v of the lane a DPP row permutation pairs this lane with): quad_perm [1,0,3,2] (0xB1), [2,3,0,1] (0x4E), row_half_mirror (0x141),
@@ -43,8 +43,8 @@ __device__ __forceinline__ float row16_sum(float v) {
   return dpp_add<0x140>(v);
 }
 
-// NPW = 3: the bf16 planes; NPW = 2: the fp16 planes of the two-plane arithmetic (lmkd_conv_set_compute_dtype(4)), a third region of the
-// weight buffer:  [32x32x16 order: W x 3 | -W x 3][16x16x32 order: W x 3 | -W x 3][16x16x32 order, fp16: W x 2 | -W x 2][max |w| : 64 bytes]
+// NPW = 3: the bf16 planes; NPW = 2: the fp16 planes of the two-plane arithmetic (lmkd_conv_set_compute_dtype(4)): the 16x16x32 regions
+// of the weight's plane buffer (wplanes.h)
 template <int TN, int NPW = 3>
 struct X3FragB16 {
   static constexpr int NT = 2 * TN;      // 16-channel blocks of this wave
@@ -52,10 +52,8 @@ struct X3FragB16 {
   __amdgpu_buffer_rsrc_t rs;
   unsigned off[NT];
   __device__ __forceinline__ void init(const void* wf, int ncols, int Kp, int col0 /* of this wave */, int lane, bool neg) {
-    const long plane_bytes = (long)ncols * Kp * 2;
-    const long copy_bytes = plane_bytes * NPW;
-    const long base = NPW == 3 ? (neg ? 9 : 6) * plane_bytes : (neg ? 14 : 12) * plane_bytes;
-    rs = x3_rsrc(reinterpret_cast<const unsigned char*>(wf) + base, copy_bytes);
+    const long n = (long)ncols * Kp, copy_bytes = n * 2 * NPW;
+    rs = x3_rsrc(reinterpret_cast<const unsigned char*>(wf) + 2 * wpl_region(n, NPW, WPL_16, neg), copy_bytes);
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
       const int nt = (col0 >> 4) + j;
@@ -75,77 +73,13 @@ struct X3FragB16 {
   }
 };
 
-// fp32 K-major packed weights Wp[col][Kp] -> the 16x16x32 fragment order, W planes followed by -W planes (3 x ncols x Kp bf16 each)
-__global__ void split_weights16_kernel(const float* __restrict__ wp, unsigned short* __restrict__ wf, int ncols, int Kp) {
-  const long total = (long)ncols * Kp;
-  const int G = Kp >> 5;
-  for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
-    const int col = (int)(idx / Kp), k = (int)(idx - (long)col * Kp);
-    const float x = wp[idx];
-    const int lane = (col & 15) + 16 * patch16_kslot((k >> 3) & 3);      // the lane group that reads this k-slot
-    const long o = ((((long)(col >> 4) * G + (k >> 5)) * 3) * 64 + lane) * 8 + (k & 7);
-    const unsigned b0 = __float_as_uint(x);
-    const float r1 = x - __uint_as_float(b0 & 0xffff0000u);
-    const unsigned b1 = __float_as_uint(r1);
-    const float r2 = r1 - __uint_as_float(b1 & 0xffff0000u);
-    const unsigned short p0 = (unsigned short)(b0 >> 16), p1 = (unsigned short)(b1 >> 16), p2 = (unsigned short)(__float_as_uint(r2) >> 16);
-    wf[o] = p0;
-    wf[o + 512] = p1;
-    wf[o + 1024] = p2;
-    const long o2 = o + total * 3;
-    wf[o2] = p0 ^ 0x8000u;
-    wf[o2 + 512] = p1 ^ 0x8000u;
-    wf[o2 + 1024] = p2 ^ 0x8000u;
-  }
-}
-
 // (the two-plane arithmetic's helpers - h2_scale, h2_split4, h2_split1 - live in h2.h: conv_patch.h uses them too)
-// the fp16 planes of the packed weights: split_weights16_kernel's fragment order with two planes per slot (W, then -W), scaled by the
-// power of two of the word behind them (max |w|, written by amax_kernel before this launch)
-__global__ void split_weights16_h2_kernel(const float* __restrict__ wp, unsigned short* __restrict__ wh, int ncols, int Kp) {
-  const long total = (long)ncols * Kp;
-  const int G = Kp >> 5;
-  const float s = h2_scale(*reinterpret_cast<const unsigned*>(wh + total * 4));
-  for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
-    const int col = (int)(idx / Kp), k = (int)(idx - (long)col * Kp);
-    const int lane = (col & 15) + 16 * patch16_kslot((k >> 3) & 3);
-    const long o = ((((long)(col >> 4) * G + (k >> 5)) * 2) * 64 + lane) * 8 + (k & 7);
-    unsigned short p0, p1;
-    h2_split1(wp[idx] * s, p0, p1);
-    wh[o] = p0;
-    wh[o + 512] = p1;
-    const long o2 = o + total * 2;
-    wh[o2] = p0 ^ 0x8000u;
-    wh[o2 + 512] = p1 ^ 0x8000u;
-  }
-}
-// ... and in conv_x3.h's 32x32x16 fragment order (X3FragB with two planes; W only - the stem's forward, the one two-plane kernel on that
-// MFMA shape, has no -W tiles), behind the maximum's 64 bytes: wh32 = wh + 4 * total + 32
-__global__ void split_weights_h2_32_kernel(const float* __restrict__ wp, unsigned short* __restrict__ wh, int ncols, int Kp) {
-  const long total = (long)ncols * Kp;
-  const int G = Kp >> 4;
-  const float s = h2_scale(*reinterpret_cast<const unsigned*>(wh + total * 4));
-  unsigned short* wh32 = wh + total * 4 + 32;
-  for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
-    const int col = (int)(idx / Kp), k = (int)(idx - (long)col * Kp);
-    const int lane = (col & 31) + 32 * ((k >> 3) & 1);
-    const long o = ((((long)(col >> 5) * G + (k >> 4)) * 2) * 64 + lane) * 8 + (k & 7);
-    unsigned short p0, p1;
-    h2_split1(wp[idx] * s, p0, p1);
-    wh32[o] = p0;
-    wh32[o + 512] = p1;
-  }
-}
-// max |x| over n floats folded into *word (the fp32 bits of a non-negative number order like unsigned integers); *word zeroed by the caller
-// SLOTS: into the slots of an activation maximum (amax_commit); else into the one word of a weight pack
-template <bool SLOTS>
+// max |x| over n floats folded into the slots of an activation maximum at `word` (amax_commit), zeroed by the caller (lmkd_amax; the
+// maximum of a weight pack is wplanes.h's)
 __global__ void amax_kernel(const float* __restrict__ x, long n, unsigned* __restrict__ word) {
   float m = 0.f;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) m = fmaxf(m, fabsf(x[i]));
-  if (SLOTS) { amax_commit(word, m); return; }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-  if ((threadIdx.x & 63) == 0) atomicMax(word, __float_as_uint(m));
+  amax_commit(word, m);
 }
 
 // the offset table s_adp of a tile (conv_patch16_x3_kernel): row r of the tile, every tap -> patch offset in units of 16 bytes (the zero row
@@ -259,7 +193,7 @@ __global__ __launch_bounds__(Cfg::THREADS, Cfg::MINW) void conv_patch16_x3_kerne
   bool h2_one = true;
   if constexpr (NPROD == 3) {
     h2_sx = h2_scale(amax_read(a.h2_xw, sg.seg));      // the operand's maximum over this tile's frame segment
-    const float sw = h2_scale(*reinterpret_cast<const unsigned*>(reinterpret_cast<const unsigned short*>(a.wpk) + (long)a.Co * a.Kp * 16));
+    const float sw = h2_scale(*reinterpret_cast<const unsigned*>(reinterpret_cast<const unsigned short*>(a.wpk) + wpl_amax((long)a.Co * a.Kp)));
     h2_ix = 1.f / h2_sx;      // exact: powers of two within 2^+-126
     h2_iw = 1.f / sw;
     const int ex = (int)((__float_as_uint(h2_ix) >> 23) & 0xffu) + (int)((__float_as_uint(h2_iw) >> 23) & 0xffu) - 254;

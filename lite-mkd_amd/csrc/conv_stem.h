@@ -19,7 +19,7 @@
 
 // OR: output rows per workgroup (2: eight waves, 1: four waves)
 // NPROD == 3: two fp16 planes, three products (conv_patch16.h: h2_split4; lmkd_conv_set_compute_dtype(4)): the weights' fp16 planes in
-// this kernel's 32x32x16 fragment order are the last region of the weight buffer (split_weights_h2_32_kernel)
+// this kernel's 32x32x16 fragment order are the last region of the weight's plane buffer (wplanes.h; X3FragB with two planes reads it)
 template <int NPROD, bool OUT16, int OR>
 __global__ __launch_bounds__(256 * OR) void conv_stem_patch_kernel(ConvGemmArgs a) {
   constexpr int NPL = NPROD == 1 ? 1 : (NPROD == 3 ? 2 : 3);
@@ -38,13 +38,10 @@ __global__ __launch_bounds__(256 * OR) void conv_stem_patch_kernel(ConvGemmArgs 
   const int plane_bytes = PR * WP * 8;
   const int ih0 = 2 * oh0 - 3;
   float h2_sx = 1.f, h2_ix = 1.f, h2_iw = 1.f;
-  const unsigned short* wpk = reinterpret_cast<const unsigned short*>(a.wpk);
   if constexpr (NPROD == 3) {
-    const long nw = (long)a.Co * a.Kp;
     h2_sx = h2_scale(amax_read(a.h2_xw, (a.seg_m0 > 0 && (long)n * a.Ho * a.Wo >= a.seg_m0) ? 1 : 0));      // this image's frame segment
     h2_ix = 1.f / h2_sx;
-    h2_iw = 1.f / h2_scale(*reinterpret_cast<const unsigned*>(wpk + nw * 16));
-    wpk += nw * 16 + 32;
+    h2_iw = 1.f / h2_scale(*reinterpret_cast<const unsigned*>(reinterpret_cast<const unsigned short*>(a.wpk) + wpl_amax((long)a.Co * a.Kp)));
   }
   // ---- patch: input rows ih0 .. ih0 + PR - 1, columns -3 .. WP - 4, zero outside the image.  Thread -> (column, row parity);
   // every thread's loads are issued before the first one is split (a load -> split -> store loop waits one memory latency per trip)
@@ -97,7 +94,7 @@ __global__ __launch_bounds__(256 * OR) void conv_stem_patch_kernel(ConvGemmArgs 
     a_off = ((2 * orow) * WP + 2 * ow + 2 * (lane >> 5)) * 8;
   }
   LB lb;
-  lb.init(wpk, a.Co, a.Kp, 0, lane);
+  lb.init(a.wpk, a.Co, a.Kp, 0, lane);
   f32x16 acc[1][Cfg::TN];
 #pragma unroll
   for (int j = 0; j < Cfg::TN; ++j)

@@ -81,15 +81,16 @@ struct X3FragB {
   static constexpr int NR = TN * 2 * NPL;
   __amdgpu_buffer_rsrc_t rs;
   unsigned off[TN];     // byte offset of (n-tile, k-group 0, plane 0, this lane)
-  // neg: fetch the NEGATED copy of the planes (three-plane modes: lmkd_conv2d_split_weights writes it behind the plain copy).
+  // wf: the weight's plane buffer (wplanes.h); this reads its 32x32x16 region of NPL planes.
+  // neg: fetch the NEGATED copy of the planes (three-plane modes).
   // The MFMA's addition of products 2^-8 ... 2^-16 smaller than its accumulator truncates toward -inf (measured: a mean error of
   // -4e-11 x K x rms per element in the three-plane modes, none with one plane, none on the fp32 pipe: tools/x3_bias_probe.py) - half an
   // fp32 ulp at most, but of ONE sign, so the per-channel sums over 10^5 .. 10^6 pixels of the BatchNorm backward pick it up
   // coherently.  The workgroups of half the row tiles (x3_neg_tile) therefore accumulate -y (negated weights) and flip the sign in the
   // epilogue: the bias has either sign on half the pixels and cancels in every sum over pixels.
   __device__ __forceinline__ void init(const void* wf, int ncols, int Kp, int col0 /* of this wave */, int lane, bool neg = false) {
-    const long copy_bytes = (long)ncols * Kp * 2 * NPL;
-    rs = x3_rsrc(reinterpret_cast<const unsigned char*>(wf) + (neg ? copy_bytes : 0), copy_bytes);
+    const long n = (long)ncols * Kp, copy_bytes = n * 2 * NPL;
+    rs = x3_rsrc(reinterpret_cast<const unsigned char*>(wf) + 2 * wpl_region(n, NPL, WPL_32, neg), copy_bytes);
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
       const int nt = (col0 >> 5) + j;
@@ -601,36 +602,4 @@ __global__ __launch_bounds__(Cfg::THREADS) void conv_gemm_x3_kernel(ConvGemmArgs
   }
 
   x3_epilogue<Cfg, STATS, OUT16, EP>(a, acc, s_out, s_red, rt, n0, wm, wn, lane, tid, neg);
-}
-
-// fp32 K-major packed weights Wp[col][Kp] -> fragment-order bf16 planes (layout: X3FragB); npl = 1: one RNE-rounded plane;
-// npl = 3: the three planes of W followed by the three planes of -W (2 x 3 x ncols x Kp bf16)
-__global__ void split_weights_kernel(const float* __restrict__ wp, unsigned short* __restrict__ wf, int ncols, int Kp, int npl) {
-  const long total = (long)ncols * Kp;
-  const int G = Kp >> 4;
-  for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
-    const int col = (int)(idx / Kp), k = (int)(idx - (long)col * Kp);
-    const float x = wp[idx];
-    const int lane = (col & 31) + 32 * ((k >> 3) & 1);
-    const long o = ((((long)(col >> 5) * G + (k >> 4)) * npl) * 64 + lane) * 8 + (k & 7);
-    if (npl == 1) {
-      union { __bf16 h; unsigned short u; } c;
-      c.h = (__bf16)x;
-      wf[o] = c.u;
-    } else {
-      const unsigned b0 = __float_as_uint(x);
-      const float r1 = x - __uint_as_float(b0 & 0xffff0000u);
-      const unsigned b1 = __float_as_uint(r1);
-      const float r2 = r1 - __uint_as_float(b1 & 0xffff0000u);
-      const unsigned short p0 = (unsigned short)(b0 >> 16), p1 = (unsigned short)(b1 >> 16), p2 = (unsigned short)(__float_as_uint(r2) >> 16);
-      wf[o] = p0;
-      wf[o + 512] = p1;
-      wf[o + 1024] = p2;
-      // second copy: the planes of -W (sign bit flipped: the truncation split is symmetric), read by the odd row tiles (X3FragB::init)
-      const long o2 = o + total * 3;
-      wf[o2] = p0 ^ 0x8000u;
-      wf[o2 + 512] = p1 ^ 0x8000u;
-      wf[o2 + 1024] = p2 ^ 0x8000u;
-    }
-  }
 }

@@ -720,11 +720,10 @@ def _pack_weights(w, Cs, mode, out=None):
         wp = out if out is not None else _empty((n,), w)
         lib().call("lmkd_conv2d_pack_weights", _p(w), _p(wp), Cout, Cin, Cs, KH, KW, mode, _stream())
         return wp
-    # bf16 (one RNE plane) / fp32-as-3xbf16 (three planes): weights in MFMA fragment order, fetched into registers
+    # every other arithmetic: the weight's plane buffer - 16-bit planes in MFMA fragment order, fetched into registers (layout: DESIGN.md 3.1)
     wp = _empty((n,), w)
     lib().call("lmkd_conv2d_pack_weights", _p(w), _p(wp), Cout, Cin, Cs, KH, KW, mode, _stream())
     ncols = Cout if mode == 0 else Cin
-    # one RNE plane, or the planes of W and of -W in both fragment orders (lmkd_conv2d_split_weights: 2 orders x 2 signs x 3 planes)
     planes = out if out is not None else torch.empty((lib().value("lmkd_conv2d_plane_elems", ncols, n // ncols),), dtype=torch.int16, device=w.device)
     lib().call("lmkd_conv2d_split_weights", _p(wp), planes.data_ptr(), ncols, n // ncols, _stream())
     return planes

@@ -7,10 +7,15 @@ against the oracle, 64 px ... 400 frames of 224^2), tests/test_gpu_merged.py / t
 Here: what is specific to the mode - the maxima the producers record, the weight packs, and the corners of the scaling (zero tensors,
 tiny / huge magnitudes, one outlier dominating the maximum, maxima that are exact powers of two)."""
 import ctypes
+import os
+import sys
 
 import pytest
 import torch
 import torch.nn.functional as F
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _wplanes_ref as R  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -101,9 +106,10 @@ def test_weight_planes_repack_equals_split(dev):
     L.call("lmkd_conv2d_repack_multi", wp, wf, dims, m, None)
     torch.cuda.synchronize()
     for e, o in zip(ents, outs):
-        n = (e[3].numel() - 32) // 18      # 12 n bf16 planes, 4 n fp16 planes (16x16x32 order), the maximum's 64 bytes, 2 n fp16 planes (32x32x16 order)
-        assert torch.equal(o[:16 * n + 2], e[3][:16 * n + 2]) and torch.equal(o[16 * n + 32:], e[3][16 * n + 32:]), tuple(e[0].shape)
-        assert float(o[16 * n:16 * n + 2].view(torch.float32)) == float(e[0].abs().max())
+        word, end = R.regions(e[0].numel(), "fp32h2")["amax"]      # (every pack here is unpadded: as many elements as the weight)
+        assert o.numel() == R.total(e[0].numel(), "fp32h2")
+        assert torch.equal(o[:word + 2], e[3][:word + 2]) and torch.equal(o[end:], e[3][end:]), tuple(e[0].shape)
+        assert float(o[word:word + 2].view(torch.float32)) == float(e[0].abs().max())
 
 
 def _conv3(x, w, dy, seg=0):

@@ -1798,6 +1798,59 @@ def test_repack_multi_bit_identical_to_pack_and_split(dev, mode):
         ops.reset_compute_dtypes()
 
 
+@pytest.mark.parametrize("arith", ["bf16", "fp32x3", "fp32x3_9", "fp32h2"])
+def test_weight_planes_match_the_layout_statement(dev, arith):
+    """What ops._pack_weights and lmkd_conv2d_repack_multi write into sentinel-filled buffers equals, bit for bit, the numpy statement of
+    the layout (tests/_wplanes_ref.py) - every region, both fragment orders, both pack modes, at the smallest shapes that exercise every
+    stride of the index maps: the channel-padded stem (KWp = 8, Kp = 224), Kp = 288 / 576, three 32-column tiles, and Kp = 96 (an odd
+    number of 32-wide k-groups).  Values: N(0, 0.05), the same x 3 and x 1e-4, max |w| = 0.25 exactly (the power-of-two branch of the
+    fp16 planes' scale), all zeros.  41 entries in one call: one more than a launch of lmkd_conv2d_repack_multi holds.  In fp32h2 the 30
+    halfwords behind the max |w| word are unspecified and left out of the comparison."""
+    import ctypes
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import _wplanes_ref as R
+    from litemkd_amd import ops
+    shapes = [((64, 3, 7, 7), 4, 0), ((64, 32, 3, 3), 32, 0), ((64, 32, 3, 3), 32, 1), ((96, 64, 1, 1), 64, 0), ((96, 64, 1, 1), 64, 1)]
+    ents = []
+    for i in range(41):
+        shp, cs, md = shapes[i % 5]
+        kind = (i // 5) % 5
+        w = (np.random.default_rng(200 + i).standard_normal(shp) * 0.05).astype(np.float32)
+        if kind in (1, 2):
+            w *= np.float32(3.0 if kind == 1 else 1e-4)
+        elif kind == 3:
+            w = np.clip(w, -0.125, 0.125)
+            w.flat[w.size // 2] = -0.25
+        elif kind == 4:
+            w[:] = 0.0
+        ents.append((w, cs, md) + R.planes(w, cs, md, arith))
+    ops.set_conv_compute_dtype(arith)
+    try:
+        ws = [torch.from_numpy(e[0]).to(dev) for e in ents]
+        fill = lambda e: torch.full((e[3].size,), R.SENTINEL - 65536, dtype=torch.int16, device=dev)      # noqa: E731
+        one = [ops._pack_weights(w, e[1], e[2], out=fill(e)) for w, e in zip(ws, ents)]
+        many = [fill(e) for e in ents]
+        m = len(ents)
+        a = (ctypes.c_void_p * m)(*[w.data_ptr() for w in ws])
+        b = (ctypes.c_void_p * m)(*[o.data_ptr() for o in many])
+        d = (ctypes.c_int * (6 * m))(*[v for e in ents for v in e[0].shape[:2] + (e[1],) + e[0].shape[2:] + (e[2],)])
+        ops.lib().call("lmkd_conv2d_repack_multi", a, b, d, m, ops._stream())
+        torch.cuda.synchronize()
+        for i, e in enumerate(ents):
+            want, reg = e[3], e[4]
+            keep = np.ones(want.size, bool)
+            if arith == "fp32h2":
+                keep[reg["amax"][0] + 2:reg["amax"][1]] = False
+            for name, got in (("pack + split", one[i]), ("repack_multi", many[i])):
+                g = got.cpu().numpy().view(np.uint16)
+                bad = np.flatnonzero((g != want) & keep)
+                where = [k for k, (lo, hi) in reg.items() if bad.size and lo <= bad[0] < hi]
+                assert bad.size == 0, (arith, name, i, e[0].shape, e[1], e[2], int(bad.size), where)
+    finally:
+        ops.reset_compute_dtypes()
+
+
 @pytest.mark.parametrize("mode", ["fp32x3", "bf16"])
 def test_trx_projections_on_conv_kernels_match_gemm(dev, mode):
     """ops.TRX_PROJ_ON_CONV (opt-in): the TRX projections and their input gradient as 1x1 convolutions in the three-plane arithmetic -
