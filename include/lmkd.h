@@ -409,6 +409,25 @@ int lmkd_adam_step(float* param, float* grad, float* exp_avg, float* exp_avg_sq,
                    long step, long n, int zero_grad, void* stream);
 int lmkd_fill(float* p, float v, long n, void* stream);
 
+/* ---- the clip classifier the teacher's per-modality ResNet-50 is pretrained as (csrc/clipcls.hip; reference teacher/code/model.py
+ * Action_Recognition_Resnet50, pretrain/pretrain.py) ----
+ * global average pool: x [F, H, W, C] NHWC in the trunk's storage type (lmkd_set_activation_dtype) -> y [F/G, C] fp32 = the mean over the
+ * H*W positions and over groups of G consecutive frames (G = 1: per-frame features; G = T: the clip feature, the mean over frames of
+ * per-frame means being the mean over G*H*W positions); backward dx[f,h,w,c] = dy[f/G, c] / (G*H*W).  F % G == 0, C % 4 == 0, 16-byte
+ * aligned tensors.  Fixed summation order: repeats are bit-identical. */
+int lmkd_global_avgpool_fwd(const float* x, float* y, int F, int H, int W, int C, int G, void* stream);
+int lmkd_global_avgpool_bwd(const float* dy, float* dx, int F, int H, int W, int C, int G, void* stream);
+/* nn.CrossEntropyLoss (mean) over [R, C] fp32 logits and int64 labels, any C >= 1: out2 = {mean loss, accuracy}, pred (nullable) [R] =
+ * first maximal index, g (nullable) [R, C] = (softmax - onehot) / R; rows: [2 R] floats of scratch (per-row loss and hit).  labels_host
+ * (nullable): a host copy of the labels; one outside [0, C) returns the error code before anything is launched.  The kernel never
+ * indexes with a label outside the range (that row's loss is NaN). */
+int lmkd_softmax_ce(const float* logits, const long long* labels, const long long* labels_host, float* out2, long long* pred, float* g,
+                    float* rows, int R, int C, void* stream);
+/* torch.optim.SGD(momentum, dampening 0, no Nesterov, no weight decay): buf = first ? grad : momentum * buf + grad; param -= lr * buf;
+ * grad = 0 when zero_grad.  16-byte aligned buffers, n % 4 == 0 (lmkd_sgd_step's contract). */
+int lmkd_sgd_momentum_step(float* param, float* grad, float* buf, float lr, float momentum, long n, int first, int zero_grad,
+                           void* stream);
+
 /* ---- both trunk calls of an episode in ONE launch per layer (round 4) ----
  * The reference calls the trunk twice per episode with the same weights and shapes - self.resnet(context_images) and
  * self.resnet(target_images), model/backbone/resnet18_2fc.py:41-42 - and train-mode BatchNorm gives each call its own batch statistics.

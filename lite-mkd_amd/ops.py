@@ -2772,6 +2772,82 @@ def accuracy(l1, l2, labels):
     return acc[0], pred
 
 
+class GlobalAvgPoolFn(torch.autograd.Function):
+    """AdaptiveAvgPool2d(1) of the torchvision ResNet-50 the teacher's per-modality model is built on, and the mean over `group`
+    consecutive frames with it (Action_Recognition_Resnet50.forward: the mean over a clip's frames of the per-frame means).
+    NHWC [F, H, W, C] in the trunk's storage type -> [F / group, C] fp32."""
+
+    @staticmethod
+    def forward(ctx, x, group=1):
+        _chk(x)
+        F_, H, W, C = x.shape
+        group = int(group)
+        if x.dtype is not _ACT_DTYPE[0]:      # the kernel instance follows the process-wide storage type, not the tensor
+            raise RuntimeError("GlobalAvgPoolFn: %s input while the activation storage type is %s" % (x.dtype, get_activation_dtype()))
+        if group < 1 or F_ % group:
+            raise RuntimeError("GlobalAvgPoolFn: %d frames are no multiple of the group of %d" % (F_, group))
+        y = _empty((F_ // group, C), x)
+        lib().call("lmkd_global_avgpool_fwd", _p(x), _p(y), F_, H, W, C, group, _stream())
+        ctx.shape, ctx.group, ctx.act = (F_, H, W, C), group, (x.dtype, x.device)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        _audit.engine_owned(dy)
+        F_, H, W, C = ctx.shape
+        dy = dy.contiguous()
+        _chk(dy)
+        dx = torch.empty(ctx.shape, dtype=ctx.act[0], device=ctx.act[1])
+        lib().call("lmkd_global_avgpool_bwd", _p(dy), _p(dx), F_, H, W, C, ctx.group, _stream())
+        return dx, None
+
+
+class SoftmaxCEFn(torch.autograd.Function):
+    """nn.CrossEntropyLoss (mean) with the accuracy and the predictions of the same pass -> ([2] tensor: loss, accuracy; predictions).
+    The logits gradient is written by the forward launch; the backward scales it (D2MLossFn's arrangement)."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, labels_host):
+        R, C = logits.shape
+        out = _empty((2,), logits)
+        pred = torch.empty((R,), dtype=torch.int64, device=logits.device)
+        g = torch.empty_like(logits) if ctx.needs_input_grad[0] else None
+        rows = _empty((2 * R,), logits)
+        host = ctypes.c_void_p(labels_host.data_ptr()) if labels_host is not None else None
+        lib().call("lmkd_softmax_ce", _p(logits), _p(labels), host, _p(out), _p(pred), _p(g), _p(rows), R, C, _stream())
+        ctx.g = g
+        ctx.mark_non_differentiable(pred)
+        return out, pred
+
+    @staticmethod
+    def backward(ctx, gout, _gpred):
+        _audit.engine_owned(gout)
+        return ctx.g * gout[0], None, None      # only the loss carries gradient
+
+
+def softmax_ce(logits, labels, with_pred=False):
+    """criterion(output, label) of pretrain.py (nn.CrossEntropyLoss) for any number of classes -> (loss, accuracy) as 0-dim tensors, the
+    loss with its autograd graph; with_pred: (loss, accuracy, predictions).  labels: int64 [R].  Labels on the host are range-checked
+    there (a label outside [0, C) raises before anything is launched) and go up through pinned memory; labels already on the device are
+    not read back - the kernel indexes with none outside the range and that row's loss is NaN."""
+    if logits.dim() != 2 or labels.dim() != 1 or labels.shape[0] != logits.shape[0]:
+        raise RuntimeError("softmax_ce: logits [R, C] and labels [R] expected, got %s and %s" % (tuple(logits.shape), tuple(labels.shape)))
+    if labels.dtype != torch.int64:
+        raise RuntimeError("labels must be int64")
+    if logits.dtype != torch.float32:
+        raise RuntimeError("softmax_ce: fp32 logits expected, got %s" % logits.dtype)
+    logits = logits.contiguous()
+    _chk(logits)
+    host = None
+    if not labels.is_cuda:
+        host = labels.contiguous()
+        labels = h2d_async(host, logits.device)
+    labels = labels.contiguous()
+    _chk(labels)
+    out, pred = SoftmaxCEFn.apply(logits, labels, host)
+    return (out[0], out[1].detach(), pred) if with_pred else (out[0], out[1].detach())
+
+
 _plan_cache = [None, None, None]
 _cpu_labels = [None, None]
 _PLANS_BY_CPU = {}      # (id of the CPU label tensor, its _version, way) -> (weakref, plan): a resident episode pool re-uses its plans

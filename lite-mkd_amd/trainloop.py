@@ -88,6 +88,101 @@ class MultiStepLR:
         self.opt.lr = self.base * self.gamma ** sum(1 for m in self.milestones if m <= self.n)
 
 
+class MomentumSGD:
+    """torch.optim.SGD(momentum, dampening 0, no Nesterov, no weight decay) over the flat buffers, with one (lr, momentum) per named
+    parameter group: pretrain.py's two optimizers (the trunk at lr_1, fc at lr_2) as one object.  groups: {name: (prefix of the parameter
+    names, lr, momentum)}; every trainable parameter belongs to exactly one group.  A group's parameters lie next to each other in the
+    flat buffer (module order), so a step is one lmkd_sgd_momentum_step launch per group and contiguous run of it - one per group for
+    Action_Recognition_Resnet50."""
+
+    def __init__(self, module, groups):
+        names = [n for n, p in module.named_parameters() if p.requires_grad]
+        self.bucket = FlatParams(module)
+        if len(names) != len(self.bucket.params):
+            raise ValueError("a parameter is registered under two names: the groups are told apart by name")
+        self.buf = torch.zeros_like(self.bucket.flat)
+        self.groups = {}
+        owner = []
+        for n in names:
+            hit = [g for g, (prefix, _, _) in groups.items() if n.startswith(prefix)]
+            if len(hit) != 1:
+                raise ValueError("parameter %s belongs to %d groups (%s)" % (n, len(hit), ", ".join(hit) or "none"))
+            owner.append(hit[0])
+        ends = self.bucket.offsets[1:] + [self.bucket.numel]
+        for g, (prefix, lr, momentum) in groups.items():
+            runs = []
+            for o, e, own in zip(self.bucket.offsets, ends, owner):
+                if own != g:
+                    continue
+                if runs and runs[-1][1] == o:
+                    runs[-1][1] = e
+                else:
+                    runs.append([o, e])
+            if not runs:
+                raise ValueError("group %s (prefix %r) holds no trainable parameter" % (g, prefix))
+            self.groups[g] = {"lr": float(lr), "momentum": float(momentum), "steps": 0, "runs": [tuple(r) for r in runs]}
+
+    def zero_grad(self):
+        ops.join_all_streams()
+        self.bucket.zero_grad()
+
+    def step(self, zero_grad=False):
+        """one update of every group; zero_grad: the kernels also zero the gradients they have read"""
+        b = self.bucket
+        ops.join_all_streams()              # every stream that writes the gradient buffer or its shadow, or reads the packs re-packed below
+        b.fold_shadow()
+        ops.WEIGHT_EPOCH[0] += 1            # invalidates the packed-weight cache (raw-pointer update below)
+        s = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        es = b.flat.element_size()
+        P = lambda t, o: ctypes.c_void_p(t.data_ptr() + o * es)       # noqa: E731
+        for g in self.groups.values():
+            for o, e in g["runs"]:
+                lib().call("lmkd_sgd_momentum_step", P(b.flat, o), P(b.grad, o), P(self.buf, o), ctypes.c_float(g["lr"]),
+                           ctypes.c_float(g["momentum"]), e - o, int(g["steps"] == 0), int(zero_grad), s)
+            g["steps"] += 1
+        if REPACK_AT_STEP:
+            ops.refresh_packs()
+
+    def _cat(self, g):
+        return torch.cat([self.buf[o:e] for o, e in self.groups[g]["runs"]])
+
+    def state(self, group):
+        """what a checkpoint keeps of one group (pretrain.py's optimizer1_state_dict / optimizer2_state_dict)"""
+        g = self.groups[group]
+        return {"lr": g["lr"], "momentum": g["momentum"], "steps": g["steps"], "momentum_buffer": self._cat(group).cpu()}
+
+    def load_state(self, group, s):
+        g = self.groups[group]
+        mb = s["momentum_buffer"]
+        if mb.numel() != sum(e - o for o, e in g["runs"]):
+            raise ValueError("group %s: a momentum buffer of %d elements, this model's group holds %d" % (group, mb.numel(), sum(e - o for o, e in g["runs"])))
+        g["lr"], g["momentum"], g["steps"] = float(s["lr"]), float(s["momentum"]), int(s["steps"])
+        at = 0
+        for o, e in g["runs"]:
+            self.buf[o:e].copy_(mb[at:at + e - o])
+            at += e - o
+
+
+class StepLR:
+    """torch.optim.lr_scheduler.StepLR(step_size, gamma) on one group of a MomentumSGD: after n calls of step() the group's learning rate
+    is base * gamma ** (n // step_size)"""
+
+    def __init__(self, optimizer, group, step_size=10, gamma=0.1):
+        self.opt, self.group, self.step_size, self.gamma, self.n = optimizer, group, int(step_size), gamma, 0
+        self.base = optimizer.groups[group]["lr"]
+
+    def step(self):
+        self.n += 1
+        self.opt.groups[self.group]["lr"] = self.base * self.gamma ** (self.n // self.step_size)
+
+    def state(self):
+        return {"n": self.n, "base": self.base, "step_size": self.step_size, "gamma": self.gamma}
+
+    def load_state(self, s):
+        self.n, self.base, self.step_size, self.gamma = int(s["n"]), float(s["base"]), int(s["step_size"]), float(s["gamma"])
+        self.opt.groups[self.group]["lr"] = self.base * self.gamma ** (self.n // self.step_size)
+
+
 def prepare_task(task_dict, device, images_to_device=True):
     """trainwandb.py:419-443"""
     context_images, context_labels = task_dict["support_set"][0], task_dict["support_labels"][0]
