@@ -551,6 +551,26 @@ int lmkd_ctx_attend_bwd(const float* dlogits, const float* K, const float* V, co
                         float* dK, float* dV, int Ns, int Nq, int way, int L, int D, int nseg, const int* seg_off, const int* seg_cnt,
                         const int* seg_col, void* stream);
 
+/* ---- attention maps of the students (heatmap_vis.py:20-48, teacher/code/heatmap_vis.py:16-27: Grad-CAM on layer4, laid over the
+ * frame); csrc/cam.hip.  The reference goes through pytorch_grad_cam and cv2 on a torchvision network; the arithmetic is defined here.
+ * Fixed-order reductions, no atomics: two calls on the same inputs are bit-identical. */
+/* heatmap_vis.py:26-33 (GradCAM(model, target_layers)(input_tensor, targets)).  A, dA [F][HW][C] = the map entering the pooled head and
+   the gradient of the class score with respect to it.  mode 0 (Grad-CAM): w[f][c] = (sum_p dA[f][p][c]) / HW,
+   raw[f][p] = max(0, sum_c w[f][c] A[f][p][c]); mode 1 (HiResCAM): raw[f][p] = max(0, sum_c dA[f][p][c] A[f][p][c]).  Both:
+   cam[f][p] = (raw[f][p] - min_p raw) / (1e-7 + (max_p raw - min_p raw)) - the range first, so a constant map gives zeros in fp32 too.  weights [F][C] (nullable) receives
+   w in either mode; raw, cam [F][HW].  One launch, one workgroup per frame, A and dA read once each.  C a multiple of 8 up to 4096,
+   1 <= HW <= 2048, mode 0 | 1: anything else returns non-zero, naming the argument, before any launch. */
+int lmkd_gradcam_fwd(const float* A, const float* dA, float* weights, float* raw, float* cam, int F, int HW, int C, int mode, void* stream);
+/* heatmap_vis.py:35-48 (show_cam_on_image: colour map, blend with the frame; teacher/code/heatmap_vis.py:23-27).  cam [F][h][w] in [0, 1]
+   -> q = min(255, (int)(cam * 255 + 0.5f)) -> h x w to Ho x Wo with Pillow's two-pass 8-bit bilinear resampler (bounds_h / coeffs_h:
+   lmkd_resize_plan(w, Wo) uploaded, bounds_v / coeffs_v: lmkd_resize_plan(h, Ho); horizontal pass first, uint8 between the passes, each
+   thread both passes for its own pixel as lmkd_frames_resize_crop_nhwc4) -> lut [256][3] uint8 -> out [F][Ho][Wo][3] uint8 =
+   (lut * (256 - alpha256) + frames * alpha256 + 128) >> 8 with frames [F][Ho][Wo][3] uint8 RGB; frames null: the coloured map alone.
+   alpha256 in [0, 256], F <= 65535.  One launch, one thread per output pixel. */
+int lmkd_cam_overlay_u8(const float* cam, const unsigned char* frames, unsigned char* out, const int* bounds_h, const int* coeffs_h,
+                        int ksize_h, const int* bounds_v, const int* coeffs_v, int ksize_v, const unsigned char* lut, int F, int h, int w,
+                        int Ho, int Wo, int alpha256, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,6 +10,7 @@ Layout mirrors the reference for the path it replaces:
   parallel.py             episode-parallel data parallelism: flat gradient bucket + RCCL all-reduce
   teacher/                the MFM fusions (mfm.py) and the per-modality extractor Action_Recognition_Resnet50 (action_recognition.py)
   pretrain.py, extract.py the teacher's pretrain/pretrain.py loop and its two feature extraction scripts
+  cam.py, heatmap.py      Grad-CAM / HiResCAM maps of a student on its last trunk stage and their overlays (heatmap_vis.py)
   csrc/ + ops.py + _lib.py   HIP kernels, their C ABI (include/lmkd.h) and the autograd glue
 
 Import name: `litemkd_amd` (the directory name has a hyphen; litemkd_amd.py at the repo root

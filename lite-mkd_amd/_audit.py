@@ -27,6 +27,7 @@ _open = {}         # (storage address, stream) -> findings waiting for a record_
 _pending = []      # tensors named to the upcoming entry-point call
 _findings = []
 _installed = [False]
+_orig = {}         # what install() replaced: factory name -> torch's own function, "record_stream" -> Tensor.record_stream
 
 
 def _cur():
@@ -59,12 +60,12 @@ def install():
         return
     _installed[0] = True
     for name in ("empty", "empty_like", "zeros", "zeros_like", "ones", "full"):
-        orig = getattr(torch, name)
+        orig = _orig[name] = getattr(torch, name)
 
         def wrapped(*a, __orig=orig, **k):
             return _tag(__orig(*a, **k))
         setattr(torch, name, wrapped)
-    orig_rec = torch.Tensor.record_stream
+    orig_rec = _orig["record_stream"] = torch.Tensor.record_stream
 
     def record_stream(self, s):
         if self.is_cuda and self.numel() > 0:
@@ -75,6 +76,17 @@ def install():
             _open.pop((k, s.cuda_stream), None)      # recorded after the launch: resolved
         return orig_rec(self, s)
     torch.Tensor.record_stream = record_stream
+
+
+def uninstall():
+    """put torch's own factories and Tensor.record_stream back (idempotent).  For a process that goes on after an audited stretch: torch's
+    device context (`with torch.device(...)`) recognises the factories by identity and passes the wrappers by"""
+    if not _installed[0]:
+        return
+    for name, fn in _orig.items():
+        setattr(torch.Tensor if name == "record_stream" else torch, name, fn)
+    _orig.clear()
+    _installed[0] = False
 
 
 def enable(on=True, strict=False):

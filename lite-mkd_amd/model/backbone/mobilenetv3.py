@@ -155,8 +155,8 @@ def features_two_calls(mobile, context_frames, target_frames):
     feats = getattr(mobile, "0")
     training = feats.training
     upd_s, upd_q = ([], []) if training else (None, None)
-    cf = ops.PoolHeadFn.apply(feats(context_frames, upd_s))
-    tf = ops.PoolHeadFn.apply(feats(target_frames, upd_q))
+    cf = ops.pool_head(feats(context_frames, upd_s))
+    tf = ops.pool_head(feats(target_frames, upd_q))
     if training:
         ops.mnv3_running_update(upd_s, upd_q)
     return cf, tf

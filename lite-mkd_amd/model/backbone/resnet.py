@@ -285,7 +285,7 @@ def two_trunk_calls(trunk, head, context_frames, target_frames):
 
 
 class Linear(nn.Linear):
-    """nn.Linear parameters/init, forward on the MFMA GEMM."""
+    """nn.Linear parameters/init, forward on the MFMA GEMM (in blocks of `gemm_k_block` terms where ops.module_k_block set it)."""
 
     def forward(self, x):
-        return ops.LinearFn.apply(x, self.weight, self.bias)
+        return ops.LinearFn.apply(x, self.weight, self.bias, self.__dict__.get("gemm_k_block", 0))

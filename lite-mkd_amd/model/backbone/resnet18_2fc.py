@@ -17,7 +17,7 @@ class resnet18_2fc(nn.Module):
 
     def forward(self, context_feature, context_labels, target_feature):
         # two separate trunk calls = two separate BatchNorm batches (resnet18_2fc.py:41-42)
-        X, Fs = trunk_features(self.resnet, ops.PoolHeadFn.apply, context_feature, target_feature)     # :41-54: both calls, one launch per layer
+        X, Fs = trunk_features(self.resnet, ops.pool_head, context_feature, target_feature)     # :41-54: both calls, one launch per layer
         L, D = self.args.seq_len, self.args.trans_linear_in_dim
         c1, t1, c2, t2 = ops.two_head_linear_x(X, Fs, self.fc1, self.fc2)      # :56-64, one autograd node for the four calls
         context_feature_dict = {

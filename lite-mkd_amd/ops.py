@@ -325,18 +325,20 @@ FUSE_TWO_HEAD_LINEAR = True
 
 
 class TwoHeadLinearFn(torch.autograd.Function):
-    """X = the pooled features of the support frames (rows [0, Nc)) followed by those of the query frames"""
+    """X = the pooled features of the support frames (rows [0, Nc)) followed by those of the query frames.
+    k_block: gemm's, for the forward and the input gradient, as LinearFn's"""
 
     @staticmethod
-    def forward(ctx, X, Nc, w1, b1, w2, b2):
+    def forward(ctx, X, Nc, w1, b1, w2, b2, k_block=0):
         X = X.contiguous()
         M, K = X.shape
         N = w1.shape[0]
         Y1, Y2 = _empty((M, N), X), _empty((M, N), X)
-        gemm("K", "K", M, N, K, X, K, w1, K, Y1, N, bias=b1)
-        gemm("K", "K", M, N, K, X, K, w2, K, Y2, N, bias=b2)
+        gemm("K", "K", M, N, K, X, K, w1, K, Y1, N, bias=b1, k_block=k_block)
+        gemm("K", "K", M, N, K, X, K, w2, K, Y2, N, bias=b2, k_block=k_block)
         ctx.save_for_backward(X, w1, w2)
         ctx.Nc = Nc
+        ctx.k_block = k_block
         ctx.params = (w1, b1, w2, b2)
         return Y1[:Nc], Y1[Nc:], Y2[:Nc], Y2[Nc:]
 
@@ -362,7 +364,7 @@ class TwoHeadLinearFn(torch.autograd.Function):
             dX = _empty((M, K), X)
             if live:                # dX = G1 @ W1 (+ G2 @ W2 accumulated in the second GEMM's epilogue: no cat of the gradients / weights)
                 for i, (g, w) in enumerate(live):
-                    gemm("K", "N", M, K, N, g, N, w, K, dX, K, beta=0.0 if i == 0 else 1.0)
+                    gemm("K", "N", M, K, N, g, N, w, K, dX, K, beta=0.0 if i == 0 else 1.0, k_block=ctx.k_block)
             else:
                 dX.zero_()
         outs = [dX if ctx.needs_input_grad[0] else None, None]
@@ -374,13 +376,14 @@ class TwoHeadLinearFn(torch.autograd.Function):
                 if pb is not None and pb.requires_grad:
                     db = deliver_colsum(pb, g)
             outs += [dw, db]
-        return tuple(outs)
+        return tuple(outs) + (None,)
 
 
 def two_head_linear_x(X, Nc, fc1, fc2):
-    """X [Nc + Nt, K] = support-frame rows followed by query-frame rows -> fc1(X[:Nc]), fc1(X[Nc:]), fc2(X[:Nc]), fc2(X[Nc:])"""
+    """X [Nc + Nt, K] = support-frame rows followed by query-frame rows -> fc1(X[:Nc]), fc1(X[Nc:]), fc2(X[:Nc]), fc2(X[Nc:]).
+    The modules' `gemm_k_block` attribute, where set (module_k_block), is the GEMMs' k_block"""
     if FUSE_TWO_HEAD_LINEAR and X.is_cuda and X.dim() == 2 and fc1.weight.shape == fc2.weight.shape and fc1.bias is not None and fc2.bias is not None:
-        return TwoHeadLinearFn.apply(X, Nc, fc1.weight, fc1.bias, fc2.weight, fc2.bias)
+        return TwoHeadLinearFn.apply(X, Nc, fc1.weight, fc1.bias, fc2.weight, fc2.bias, fc1.__dict__.get("gemm_k_block", 0))
     cf, tf = X[:Nc], X[Nc:]
     return fc1(cf), fc1(tf), fc2(cf), fc2(tf)
 
@@ -2040,6 +2043,144 @@ class PoolHeadFn(torch.autograd.Function):
         dx = torch.empty_like(x)
         lib().call("lmkd_adaptive_maxpool_mean_bwd", _p(x), _p(dy.contiguous()), _p(dx), F_, H, W, C, _stream())
         return dx
+
+
+# ------------------------------------------------------------------------------------------
+# attention maps (csrc/cam.hip; heatmap_vis.py:20-48, teacher/code/heatmap_vis.py:16-27)
+# ------------------------------------------------------------------------------------------
+# The six non-STRM backbones hand their trunk's NHWC map to the pooled head through pool_head().  While a tap is active (cam.grad_cam)
+# the map is cut out of the graph there and becomes a leaf: a backward from the logits ends at it and never enters the trunk.  With no
+# tap active pool_head IS PoolHeadFn.apply.
+_CAM_TAP = [None]
+CAM_MAX_C, CAM_MAX_HW = 4096, 2048      # lmkd_gradcam_fwd's limits (csrc/cam.hip)
+CAM_GRADCAM, CAM_HIRESCAM = 0, 1
+
+
+class CamTap:
+    """the maps that entered the pooled head during one forward, as autograd leaves.  The two-call schedules (two streams, MobileNet)
+    deliver the support frames' map and then the query frames'; the merged trunk call delivers one map of both, support frames first."""
+
+    def __init__(self, n_support):
+        self.n_support = int(n_support)
+        self.leaves = []
+
+    def record(self, x):
+        if len(self.leaves) == 2:
+            raise RuntimeError("a third map reached the pooled head in one forward")
+        x = x.detach().requires_grad_()
+        self.leaves.append(x)
+        return x
+
+    def split(self, tensors=None):
+        """-> (support, query) of the recorded maps, or of `tensors` (one per recorded map: their gradients)"""
+        ts = list(self.leaves if tensors is None else tensors)
+        if len(ts) == 2:
+            s, q = ts
+        elif len(ts) == 1 and ts[0].shape[0] > self.n_support:
+            s, q = ts[0][:self.n_support], ts[0][self.n_support:]
+        elif len(ts) == 1:
+            raise RuntimeError("the one recorded map holds %d frames, the support set alone %d: no query frames reached the pooled head" % (
+                ts[0].shape[0], self.n_support))
+        else:
+            raise RuntimeError("%d maps reached the pooled head: this backbone does not pool through ops.pool_head" % len(ts))
+        if s.shape[0] != self.n_support:
+            raise RuntimeError("the first recorded map holds %d frames, the support set %d" % (s.shape[0], self.n_support))
+        return s, q
+
+
+@contextlib.contextmanager
+def cam_tap(n_support):
+    """record the maps entering the pooled head in the body's forward; the tap is cleared afterwards, also when the body raises"""
+    if _CAM_TAP[0] is not None:
+        raise RuntimeError("a Grad-CAM tap is already active")
+    tap = _CAM_TAP[0] = CamTap(n_support)
+    try:
+        yield tap
+    finally:
+        _CAM_TAP[0] = None
+
+
+@contextlib.contextmanager
+def module_k_block(root, k_block):
+    """the Linear heads and TRX matchers under `root` sum their GEMMs in blocks of k_block terms (gemm's k_block) in the body: the
+    `gemm_k_block` attribute that backbone.resnet.Linear, two_head_linear_x and TemporalCrossTransformer hand to their autograd
+    Functions (the MFM teacher sets it on its own head for good).  Every module gets it and gets its previous state back afterwards;
+    other models, threads and streams of the process are not touched"""
+    mods = [(m, m.__dict__.get("gemm_k_block")) for m in root.modules()]
+    try:
+        for m, _ in mods:
+            m.gemm_k_block = int(k_block)
+        yield
+    finally:
+        for m, prev in mods:
+            if prev is None:
+                m.__dict__.pop("gemm_k_block", None)
+            else:
+                m.gemm_k_block = prev
+
+
+def pool_head(x):
+    """AdaptiveMaxPool2d((4, 4)) + mean over the patches of the trunk's map (PoolHeadFn), through the tap when one is active"""
+    tap = _CAM_TAP[0]
+    if tap is not None:
+        x = tap.record(x)
+    return PoolHeadFn.apply(x)
+
+
+def gradcam(A, dA, mode=CAM_GRADCAM):
+    """A, dA [F, h, w, C] (or [F, HW, C]) fp32: the map entering the pooled head and the score's gradient with respect to it ->
+    (weights [F, C], raw [F, h, w], cam [F, h, w]) - mode 0 Grad-CAM, mode 1 HiResCAM (include/lmkd.h lmkd_gradcam_fwd)"""
+    _mnv3_chk(A, dA)
+    if A.dtype != torch.float32 or dA.dtype != torch.float32 or A.shape != dA.shape or A.dim() not in (3, 4):
+        raise RuntimeError("gradcam expects two fp32 tensors of one shape [F, h, w, C] or [F, HW, C]")
+    F_, C = A.shape[0], A.shape[-1]
+    HW = A.numel() // max(F_ * C, 1)
+    weights = _empty((F_, C), A)
+    raw = _empty(tuple(A.shape[:-1]), A)
+    cam = _empty(tuple(A.shape[:-1]), A)
+    lib().call("lmkd_gradcam_fwd", _p(A), _p(dA), _p(weights), _p(raw), _p(cam), F_, HW, C, int(mode), _stream())
+    return weights, raw, cam
+
+
+def jet_lut(device=None):
+    """the JET colour table [256, 3] uint8 (RGB) in integers: channel value x2 = clip(765 - |8 i - centre|, 0, 510) with centres 1530
+    (red), 1020 (green), 510 (blue), byte = (x2 + 1) >> 1"""
+    i = torch.arange(256, dtype=torch.int64)
+    lut = torch.stack([((765 - (8 * i - c).abs()).clamp(0, 510) + 1) >> 1 for c in (1530, 1020, 510)], 1).to(torch.uint8)
+    return lut if device is None else lut.to(device)
+
+
+_JET = {}
+
+
+def cam_overlay(cam, frames_u8, out_hw, image_weight=0.5, lut=None):
+    """cam [F, h, w] fp32 in [0, 1] -> uint8 [F, Ho, Wo, 3]: quantised to 8 bit, upsampled to out_hw = (Ho, Wo) as Pillow's BILINEAR does,
+    coloured through `lut` (uint8 [256, 3]; default jet_lut) and blended with frames_u8 (uint8 RGB [F, Ho, Wo, 3]; None: the coloured map
+    alone) as (colour * (256 - a) + frame * a + 128) >> 8, a = round(256 * image_weight)"""
+    _mnv3_chk(cam, frames_u8, lut)
+    Ho, Wo = (int(v) for v in out_hw)
+    if cam.dtype != torch.float32 or cam.dim() != 3:
+        raise RuntimeError("cam_overlay expects an fp32 [F, h, w] map")
+    F_, h, w = cam.shape
+    if frames_u8 is not None and (frames_u8.dtype != torch.uint8 or tuple(frames_u8.shape) != (F_, Ho, Wo, 3)):
+        raise RuntimeError("cam_overlay: frames must be uint8 [%d, %d, %d, 3]" % (F_, Ho, Wo))
+    if not 0.0 <= image_weight <= 1.0:
+        raise ValueError("image_weight %r outside [0, 1]" % (image_weight,))
+    if lut is None:
+        key = str(cam.device)
+        if key not in _JET:
+            _JET[key] = jet_lut(cam.device)
+        lut = _JET[key]
+    elif lut.dtype != torch.uint8 or tuple(lut.shape) != (256, 3):
+        raise RuntimeError("cam_overlay: lut must be uint8 [256, 3]")
+    bh, kh, ksh = _resize_plan(w, Wo, cam.device)
+    bv, kv, ksv = _resize_plan(h, Ho, cam.device)
+    out = torch.empty((F_, Ho, Wo, 3), dtype=torch.uint8, device=cam.device)
+    for f0 in range(0, F_, 65535):      # (the frame index travels in gridDim.y)
+        f1 = min(F_, f0 + 65535)
+        lib().call("lmkd_cam_overlay_u8", _p(cam[f0:f1]), _p(frames_u8[f0:f1]) if frames_u8 is not None else None, _p(out[f0:f1]),
+                   _p(bh), _p(kh), int(ksh), _p(bv), _p(kv), int(ksv), _p(lut), f1 - f0, h, w, Ho, Wo, int(round(256 * image_weight)), _stream())
+    return out
 
 
 # ------------------------------------------------------------------------------------------
