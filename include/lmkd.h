@@ -231,6 +231,33 @@ int lmkd_jpeg_decode(const unsigned char* data, const void* descs, const void* p
 /* the same routines on the CPU, every pointer HOST memory (the tests' reference; not on the training path) */
 int lmkd_jpeg_decode_host(const unsigned char* data, const void* descs, const void* pool, int n, short* coef, unsigned char* planes,
                           unsigned char* out, int* status);
+/* ---- PNG frames (teacher/code/AuxDataset.py:129-136 read_single_image = Image.open(path).convert("RGB") over os.listdir of a video
+ * folder; teacher/code/video_reader.py:190-199 the same on the teacher's episode reader), csrc/png.hip + csrc/png_core.h.  The GPU decodes
+ * non-interlaced 8-bit images of colour type 0 (gray), 2 (RGB), 3 (palette) and 6 (RGBA) into uint8 [H][W][3] equal to PIL's
+ * convert("RGB"): gray replicated, palette looked up, alpha dropped, tRNS ignored.  Adam7, depths 1/2/4/16, gray + alpha, APNG and
+ * sizes above 4096 are "unsupported" (the caller decodes them with PIL); a width or height above 65535, or more than 2^27 pixels, is
+ * "malformed", so no such size reaches info or totals.
+ * lmkd_png_plan (HOST, no device work; AuxDataset.py:129-136): the interface of lmkd_jpeg_plan, except that `data` is written: the IDAT
+ * payloads of a supported image are moved together in place (one contiguous deflate stream per image); the bytes of other images stay
+ * as they are.  Descriptors of lmkd_png_desc_bytes(), palettes into `pool` (lmkd_png_pool_bytes(n) suffices), info[5 i ..] = verdict
+ * (0 decoded on the GPU, 1 unsupported, 2 malformed), reason (lmkd_png_reason), height, width, output byte offset;
+ * totals = pool bytes used, scratch bytes, output bytes, images decoded on the GPU, largest row stride. */
+long lmkd_png_desc_bytes(void);
+long lmkd_png_pool_bytes(int n);
+const char* lmkd_png_reason(int reason);
+int lmkd_png_plan(unsigned char* data, const long long* offsets, int n, void* descs, void* pool, long pool_cap, long long* info,
+                  long long* totals);
+/* two launches on `stream` (AuxDataset.py:129-136, video_reader.py:190-199): inflate, one wave per image, into scratch (totals[1] bytes,
+ * 16-byte aligned: the filtered scanlines); unfilter + expansion to RGB + Adler-32 check, one wave per image, into `out`.  data (4-byte
+ * aligned), descs, pool = the device copies of the plan's buffers; trailer: n words of scratch; max_stride = totals[4].
+ * status[i] = 0 or what stopped image i: 1 bad block type, 2 stored LEN / NLEN mismatch, 3 bad code lengths, 4 invalid length or distance
+ * symbol, 5 distance too far back, 6 more data than the image holds, 7 data ends early, 8 filter type > 4, 9 Adler-32 mismatch, 10 data
+ * does not fit the decoder's window; unsupported / malformed images are left untouched (status 0). */
+int lmkd_png_decode(const unsigned char* data, const void* descs, const void* pool, int n, unsigned char* scratch, unsigned char* out,
+                    int* status, unsigned* trailer, long long max_stride, void* stream);
+/* the same routines on the CPU (AuxDataset.py:129-136), every pointer HOST memory (the tests' reference; not on the training path) */
+int lmkd_png_decode_host(const unsigned char* data, const void* descs, const void* pool, int n, unsigned char* scratch, unsigned char* out,
+                         int* status);
 /* amax_words (nullable; mode 4): also fold max |y| into the slots of ONE frame segment at this address (lmkd_amax_words() / 2 words) */
 int lmkd_nchw3_to_nhwc4(const float* x_nchw, float* y_nhwc4, int N, int H, int W, void* stream, void* amax_words);
 /* Ticket words: the single-launch column reductions (lmkd_bn_finalize, lmkd_bn_backward, lmkd_colsum) elect their finishing workgroup

@@ -37,7 +37,8 @@ def build_parser():
     p.add_argument("--resume", action="store_true", help="skip videos whose feature.npy exists")
     p.add_argument("--seq_len", default=8, type=int)
     # stage modality
-    p.add_argument("--path", default=None, help="frame folders <path>/<class>/<video>/*.jpg of one modality")
+    p.add_argument("--path", default=None, help="frame folders <path>/<class>/<video>/*.{jpg,jpeg,png} of one modality; non-RGB frames (depth maps) are converted as "
+                        "the reference's Image.open(path).convert('RGB') does")
     p.add_argument("--modality", default="rgb", type=str)
     p.add_argument("--traintestlist", default=None)
     p.add_argument("--split", default=3, type=int)

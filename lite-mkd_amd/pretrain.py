@@ -5,9 +5,10 @@ Action_Recognition_Resnet50; the loss ops.softmax_ce (any class count), the opti
 
 Data: the videos of {mode}list{split:02d}.txt under --traintestlist (spaces become '_', the first field of a line is <class>/<video>),
 a label being the class's index in order of first appearance in trainlist03.txt (utils.parsing_label); the frames
-<path>/<class>/<video>/*.jpg, sorted; the frame choice AuxDataset.get_seq's, which followed through is int(linspace(0, n - 1, seq_len))
+<path>/<class>/<video>/*.jpg, *.jpeg and *.png, sorted by name (any modality: a depth tree of single-channel PNGs is converted to RGB
+as AuxDataset.read_single_image does, Image.open(path).convert("RGB")); the frame choice AuxDataset.get_seq's, which followed through is int(linspace(0, n - 1, seq_len))
 in every mode and for every n (a longer video is first subsampled to seq_len files and then taken whole; a shorter one falls through to
-the same linspace, frames repeating).  Frames are decoded on the GPU (ops.jpeg_decode) and transformed by GpuFrameTransform: Resize,
+the same linspace, frames repeating).  Frames are decoded on the GPU (ops.ImagePlan: JPEG and PNG) and transformed by GpuFrameTransform: Resize,
 random flip and crop in --mode train, centre crop otherwise.  An --img_size other than 84 / 224 resizes to round(img_size * 8 / 7).
 
 The loop keeps pretrain.py as it behaves:
@@ -44,7 +45,7 @@ def _flag(v):
 
 def build_parser():
     p = argparse.ArgumentParser(description="Pretrain the teacher's per-modality ResNet-50 as a clip classifier")
-    p.add_argument("--path", type=str, help="frame folders <path>/<class>/<video>/*.jpg of one modality")
+    p.add_argument("--path", type=str, help="frame folders <path>/<class>/<video>/*.{jpg,jpeg,png} of one modality (RGB, depth, flow, ...)")
     p.add_argument("--modality", default="rgb", type=str)
     p.add_argument("--traintestlist", default="splits/pretrain/kinetics", type=str)
     p.add_argument("--split", default=3, type=int)
@@ -109,9 +110,13 @@ def class_index(traintestlist):
     return d
 
 
+FRAME_EXTENSIONS = (".jpg", ".jpeg", ".png")
+
+
 def video_frames(root, entry):
+    """the frame files of a video folder, sorted by name: *.jpg, *.jpeg, *.png (AuxDataset.py:129-136 takes every file of the folder)"""
     d = os.path.join(root, entry)
-    files = sorted(f for f in os.listdir(d) if f.endswith(".jpg"))
+    files = sorted(f for f in os.listdir(d) if f.endswith(FRAME_EXTENSIONS))
     if not files:
         raise ValueError("No frames found for video %s" % entry)
     return [os.path.join(d, f) for f in files]
@@ -124,7 +129,8 @@ def frame_transform(img_size, device):
 
 def plan_clips(root, entries, seq_len):
     """the host half of a batch: the chosen frame files of every video, read and planned for the decoder (a malformed header raises,
-    naming its file) -> ops.JpegPlan over len(entries) x seq_len frames, video-major"""
+    naming its file) -> ops.ImagePlan over len(entries) x seq_len frames, video-major.  convert_rgb: a frame the GPU does not decode
+    (grayscale JPEG, 16-bit or interlaced PNG, ...) goes through PIL's convert("RGB"), as AuxDataset.read_single_image converts"""
     names = []
     for e in entries:
         paths = video_frames(root, e)
@@ -133,13 +139,13 @@ def plan_clips(root, entries, seq_len):
     for p in names:
         with open(p, "rb") as f:
             blobs.append(f.read())
-    plan = ops.JpegPlan(blobs, names=names)
+    plan = ops.ImagePlan(blobs, names=names, convert_rgb=True)
     plan.check()
     return plan
 
 
 def load_clips(plan, n_videos, seq_len, tf, train, check=True):
-    """decode a planned batch (n_videos x seq_len JPEG frames, video-major) and transform it -> (NHWC4 [n_videos * seq_len, S, S, 4], the
+    """decode a planned batch (n_videos x seq_len JPEG / PNG frames, video-major) and transform it -> (NHWC4 [n_videos * seq_len, S, S, 4], the
     decoder's status words); check=False leaves reading them (a synchronisation) to the caller: plan.raise_on_status(status.cpu())"""
     frames, status = plan.decode(check=check)
     L = seq_len
@@ -153,7 +159,7 @@ def load_clips(plan, n_videos, seq_len, tf, train, check=True):
 class ClipBatches:
     """DataLoader(AuxDataset, batch_size, shuffle=True) with getitem get_video_with_label: every pass is a fresh permutation of the list,
     the last batch may be smaller.  A batch: (NHWC4 frames [B * T, S, S, 4] on the device, int64 labels [B] on the host, the entries).
-    The files of the next batches are read and planned (ops.JpegPlan) on `workers` host threads while the current one runs."""
+    The files of the next batches are read and planned (ops.ImagePlan) on `workers` host threads while the current one runs."""
 
     def __init__(self, args, device, shuffle=True):
         self.args, self.device, self.shuffle = args, device, shuffle

@@ -244,16 +244,20 @@ class ClipDirectoryEpisodes:
             yield self.episode()
 
 
+FRAME_EXTENSIONS = (".jpg", ".jpeg", ".png")      # decoded on the GPU (ops.ImagePlan sorts a batch by file signature)
+
+
 def jpeg_frame_index(rgb_path):
     """read_dir (video_reader.py:118-196) without the split: -> ({class: {video: [frame file names]}}, {(class, video): [paths]}) of a
-    directory <rgb_path>/<class>/<video>/<frame>.jpg or an uncompressed .zip of the same tree (a member's last three path components;
-    the paths are then member names).  Classes, videos and frames sorted; the index of a directory equals that of its .zip."""
+    directory <rgb_path>/<class>/<video>/<frame>.jpg (or .jpeg / .png) or an uncompressed .zip of the same tree (a member's last three
+    path components; the paths are then member names).  Classes, videos and frames sorted; the index of a directory equals that of its
+    .zip."""
     idx = {}
     if rgb_path.endswith(".zip"):
         with zipfile.ZipFile(rgb_path) as zf:
             for name in zf.namelist():
                 parts = name.split("/")
-                if len(parts) >= 3 and parts[-1].endswith(".jpg"):
+                if len(parts) >= 3 and parts[-1].endswith(FRAME_EXTENSIONS):
                     idx.setdefault(parts[-3], {}).setdefault(parts[-2], []).append((parts[-1], name))
     else:
         for cname in os.listdir(rgb_path):
@@ -263,7 +267,7 @@ def jpeg_frame_index(rgb_path):
             for vid in os.listdir(d):
                 vd = os.path.join(d, vid)
                 if os.path.isdir(vd):
-                    idx.setdefault(cname, {})[vid] = [(f, os.path.join(vd, f)) for f in os.listdir(vd) if f.endswith(".jpg")]
+                    idx.setdefault(cname, {})[vid] = [(f, os.path.join(vd, f)) for f in os.listdir(vd) if f.endswith(FRAME_EXTENSIONS)]
     index, paths = {}, {}
     for cname in sorted(idx):
         index[cname] = {}
@@ -287,8 +291,8 @@ def read_split_lists(traintestlist, split):
 
 
 class JpegFrameEpisodes(ClipDirectoryEpisodes):
-    """Episodes from the reference's own data layout (video_reader.VideoDataset, video_reader.py:118-485): JPEG frames
-    <rgb_path>/<class>/<video>/<frame>.jpg or an uncompressed .zip of that tree, split into train / test videos by the split lists
+    """Episodes from the reference's own data layout (video_reader.VideoDataset, video_reader.py:118-485): JPEG or PNG frames
+    <rgb_path>/<class>/<video>/<frame>.jpg (.jpeg, .png) or an uncompressed .zip of that tree, split into train / test videos by the split lists
     ({train,test}list{split:02d}.txt under `traintestlist`; without them every video serves both modes), teacher features from
     <teacher_path>/<class>/<video>/ (the first file in sorted order, a float [seq_len, 2048] .npy).
 
@@ -297,7 +301,8 @@ class JpegFrameEpisodes(ClipDirectoryEpisodes):
 
     The draws are ClipDirectoryEpisodes' own (_draw: classes, videos, frames, shuffles, then flip / crop), so a seeded run picks the same
     episode from a JPEG tree as from the .npy tree of the same decoded frames; only the seq_len selected files of a video are read.  The
-    frames are decoded on the GPU (ops.JpegPlan, csrc/jpeg.hip; bit-identical to PIL): episode() decodes and transforms on the current
+    frames are decoded on the GPU (ops.ImagePlan: csrc/jpeg.hip, csrc/png.hip; bit-identical to PIL; a frame that PIL does not decode as
+    RGB raises, since the reference's student reader, video_reader.py:334-343, does not convert): episode() decodes and transforms on the current
     stream; host_episode() hands trainloop.StreamedEpisodes the compressed bytes of the episode, packed into one pinned buffer with
     their decode plan, in place of "frames"."""
 
@@ -364,7 +369,8 @@ class JpegFrameEpisodes(ClipDirectoryEpisodes):
         from . import ops
         sup, tgt = self._draw(train)
         names = [v[2][i] for v in sup + tgt for i in v[3]]
-        plan = ops.JpegPlan([self._read(p) for p in names], names=names, ring=self._ring if torch.cuda.is_available() else None)
+        plan = ops.ImagePlan([self._read(p) for p in names], names=names, ring=self._ring if torch.cuda.is_available() else None,
+                             convert_rgb=False)
         plan.check()                        # a malformed header names its file here
         return sup, tgt, plan
 

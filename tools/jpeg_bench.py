@@ -162,10 +162,10 @@ def main():
             ds = JpegFrameEpisodes(cfg, os.path.join(tmp, "jpg"), teacher_path=os.path.join(tmp, "feat"), device="cuda")
             random.seed(0)
             for _ in range(4):
-                ds.host_episode()["jpeg"].slot["event"] = None
+                ds.host_episode()["jpeg"].release()
             t0 = time.perf_counter()
             for _ in range(16):
-                ds.host_episode()["jpeg"].slot["event"] = None
+                ds.host_episode()["jpeg"].release()
             res["host_episode_ms"] = (time.perf_counter() - t0) / 16 * 1e3
             rates = {"jpeg": [], "npy": []}
             for _ in range(a.repeats):
