@@ -422,6 +422,21 @@ int lmkd_mha_small_train_fwd(const float* qkv, const float* mask, float* out, fl
 int lmkd_mha_small_bwd(const float* qkv, const float* P, const float* mask, const float* dO, float* dqkv, int B, int L, int D, int H,
                        void* stream);
 
+/* ---- MFM teacher fusion for clips of up to LMKD_MHA_SEQ_MAX_L frames: the same three attention entry points for 1 <= L <= 16, on a
+ * second kernel family (the L <= 8 one keeps the whole score block in registers, which 16 x 16 does not fit).  Same arguments, same
+ * formulas, fp32, one workgroup per (sequence, head), no atomics, bit-identical from call to call; the L <= 8 entry points are unchanged
+ * and the two families do not give each other's bits.
+ * lmkd_mha_seq: qkv [B*L, 3D] (q | k | v) -> out [B*L, D], softmax(Q K^T / sqrt(hd)) V per head, the row maximum subtracted.
+ * lmkd_mha_seq_train_fwd: lmkd_mha_seq (bit-identical out without a mask) that also writes the probabilities before dropout,
+ *   P [B*H, 16, 16], zero in the rows and columns beyond L, and applies mask (nullable, [B*H, L, L], 0 or 1/(1-p)) to the probabilities
+ *   that multiply V.
+ * lmkd_mha_seq_bwd: lmkd_mha_small_bwd's formulas from that P [B*H, 16, 16]; every element of dqkv [B*L, 3D] is written. ---- */
+#define LMKD_MHA_SEQ_MAX_L 16
+int lmkd_mha_seq(const float* qkv, float* out, int B, int L, int D, int H, void* stream);
+int lmkd_mha_seq_train_fwd(const float* qkv, const float* mask, float* out, float* P, int B, int L, int D, int H, void* stream);
+int lmkd_mha_seq_bwd(const float* qkv, const float* P, const float* mask, const float* dO, float* dqkv, int B, int L, int D, int H,
+                     void* stream);
+
 /* ---- D2M loss (distillers.py:7-30, 295-337), accuracy (utils.py:116-121), optimizer (trainwandb.py:101-104,141-143) ---- */
 int lmkd_d2m_loss(const float* s_kl, const float* t_kl, const float* s_ce, const long long* labels, const float* s_sup,
                   const float* t_sup, int Rq, int C, int Rs, int Cs, float T, float w_kl, float w_sup, float w_ce, float* out4,

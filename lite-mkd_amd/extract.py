@@ -80,6 +80,9 @@ def args_check(parser, args):
     else:
         if not args.feature_save_path or not args.checkpoint_dir:
             parser.error("--stage fusion needs --feature_save_path and --checkpoint_dir")
+        from .ops import MFM_MAX_L
+        if not 1 <= args.seq_len <= MFM_MAX_L:
+            parser.error("--seq_len %d: the fusions take clips of 1 to %d frames" % (args.seq_len, MFM_MAX_L))
     return args
 
 

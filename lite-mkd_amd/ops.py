@@ -3999,9 +3999,21 @@ class MfmPosCatFn(torch.autograd.Function):
         return tuple(out)
 
 
+MFM_MAX_L = 16      # tokens per sequence of the fusions' attention (include/lmkd.h LMKD_MHA_SEQ_MAX_L)
+
+
+def mfm_attn_family(L):
+    """-> (infix of the lmkd_mha_<infix>* entry points, padded token count of their P) for sequences of L tokens: up to 8 tokens the
+    kernels that hold the score block in registers, from 9 to MFM_MAX_L the 16-token family"""
+    if L > MFM_MAX_L:
+        raise RuntimeError("the MFM attention takes sequences of at most MFM_MAX_L = %d tokens, not %d" % (MFM_MAX_L, L))
+    return ("small", 8) if L <= 8 else ("seq", 16)
+
+
 class MfmAttnFn(torch.autograd.Function):
-    """self-attention over L <= 8 tokens per (sequence, head): qkv [B*L, 3D] -> [B*L, D]; mask [B*H, L, L] (or None) is the dropout on the
-    probabilities.  Saved for the backward: qkv, the probabilities before dropout [B*H, 8, 8], the mask."""
+    """self-attention over L <= MFM_MAX_L tokens per (sequence, head): qkv [B*L, 3D] -> [B*L, D]; mask [B*H, L, L] (or None) is the
+    dropout on the probabilities.  Saved for the backward: qkv, the probabilities before dropout ([B*H, 8, 8] up to 8 tokens,
+    [B*H, 16, 16] beyond), the mask."""
 
     @staticmethod
     def forward(ctx, qkv, mask, L, H):
@@ -4014,10 +4026,12 @@ class MfmAttnFn(torch.autograd.Function):
         B = M // L
         if mask is not None and mask.shape != (B * H, L, L):
             raise RuntimeError("MfmAttnFn: mask %s, expected %s" % (tuple(mask.shape), (B * H, L, L)))
-        out, P = _empty((M, D), qkv), _empty((B * H, 8, 8), qkv)
-        lib().call("lmkd_mha_small_train_fwd", _p(qkv), _p(mask), _p(out), _p(P), B, L, D, H, _stream())
+        family, pad = mfm_attn_family(L)
+        out, P = _empty((M, D), qkv), _empty((B * H, pad, pad), qkv)
+        lib().call("lmkd_mha_%s_train_fwd" % family, _p(qkv), _p(mask), _p(out), _p(P), B, L, D, H, _stream())
         ctx.save_for_backward(qkv, P, mask)
         ctx.dims = (B, L, D, H)
+        ctx.family = family
         return out
 
     @staticmethod
@@ -4027,7 +4041,7 @@ class MfmAttnFn(torch.autograd.Function):
         dO = dO.contiguous()
         B, L, D, H = ctx.dims
         dqkv = torch.empty_like(qkv)
-        lib().call("lmkd_mha_small_bwd", _p(qkv), _p(P), _p(mask), _p(dO), _p(dqkv), B, L, D, H, _stream())
+        lib().call("lmkd_mha_%s_bwd" % ctx.family, _p(qkv), _p(P), _p(mask), _p(dO), _p(dqkv), B, L, D, H, _stream())
         return dqkv, None, None, None
 
 

@@ -1,7 +1,7 @@
 """MFM hierarchical multi-modal fusion of the teacher (reference: teacher/code/model.py —
 TrainablePositionalEncoding :1135-1151, ThreeTransforTemproal :1300-1331, TwoTransforFusion :1361-1392,
 ThreeTRXShiftLoopTime.extract_feature :1648-1664).  Inference (eval mode, no grad), which is how the student path
-consumes it: rgb / depth / flow ResNet-50 features [N,8,2048] -> fused teacher feature [N,8,2048].
+consumes it: rgb / depth / flow ResNet-50 features [N,L,2048] -> fused teacher feature [N,L,2048], L = seq_len <= ops.MFM_MAX_L = 16.
 
 Training (the fusions' `forward`, :1317-1323 / :1376-1385, and ThreeTRXShiftLoopTime.forward :1597-1636): `_Fusion.forward` runs the same
 arithmetic with autograd - LayerNorm and attention on the training kernels of csrc/mfm.hip through ops.MfmPosCatFn / MfmAttnFn /
@@ -10,7 +10,7 @@ MfmLayerNormFn, the five Linear layers on ops.LinearFn / LinearXFn - and the ref
 Parameters live in the same torch containers as the reference (nn.Embedding, nn.LayerNorm,
 nn.TransformerEncoder(nn.TransformerEncoderLayer(d_model, nhead, batch_first=True)), nn.Linear) so the state_dict keys
 (`three_fusion.transformer_encoder.layers.0.self_attn.in_proj_weight`, `fusion.f1.weight`, ...) match the reference's
-checkpoints; the arithmetic runs on the HIP GEMM + LayerNorm + 8-token attention kernels."""
+checkpoints; the arithmetic runs on the HIP GEMM + LayerNorm + attention kernels (csrc/mfm.hip: one family up to 8 tokens, one up to 16)."""
 import ctypes
 
 import torch
@@ -54,7 +54,8 @@ def _encoder_layer(x, layer, L, nhead):
     # library's default arithmetic, the fp32 MFMA GEMM in the native mode
     qkv = ops.linear_infer(x, at.in_proj_weight, at.in_proj_bias)
     ctx = torch.empty_like(x)
-    lib().call("lmkd_mha_small", ops._p(qkv), ops._p(ctx), M // L, L, D, nhead, ops._stream())
+    family, _ = ops.mfm_attn_family(L)
+    lib().call("lmkd_mha_" + family, ops._p(qkv), ops._p(ctx), M // L, L, D, nhead, ops._stream())
     o = ops.linear_infer(ctx, at.out_proj.weight, at.out_proj.bias)
     x = layernorm(x, layer.norm1.weight, layer.norm1.bias, o, M)
     h = ops.linear_infer(x, layer.linear1.weight, layer.linear1.bias, relu=True)
@@ -72,6 +73,11 @@ class _Fusion(nn.Module):
         self.transformer_encoder = nn.TransformerEncoder(encoder_layer, num_layers=args.trans_num)
         self.f1 = nn.Linear(in_channels * n_mod, in_channels)
         self.dropout = nn.Dropout(dropout)
+
+    def check_features(self, x):
+        """before any kernel runs: x is [N, L <= ops.MFM_MAX_L, in_channels]"""
+        if x.dim() != 3 or x.shape[2] != self.in_channels or x.shape[1] > ops.MFM_MAX_L:
+            raise ValueError("features %s: the fusion takes [N, L <= %d, %d]" % (tuple(x.shape), ops.MFM_MAX_L, self.in_channels))
 
     def dropout_shapes(self, N, L):
         """{site: (shape, p)} of every dropout of one forward over N videos of L tokens, in the order their seeds are drawn:
@@ -101,9 +107,8 @@ class _Fusion(nn.Module):
         1/(1-p); a missing site has no dropout); None: in training mode the masks are drawn, in eval mode there is no dropout."""
         if len(mods) != self.n_mod:
             raise ValueError("%d modalities for a fusion of %d" % (len(mods), self.n_mod))
+        self.check_features(mods[0])
         N, L, d = mods[0].shape
-        if d != self.in_channels or L > 8:
-            raise ValueError("features %s: the fusion takes [N, L <= 8, %d]" % (tuple(mods[0].shape), self.in_channels))
         if masks is None:
             masks = self.draw_masks(N, L, mods[0].device) if self.training else {}
         else:
@@ -125,6 +130,7 @@ class _Fusion(nn.Module):
     def extract_feature(self, *mods):
         if self.training:
             raise NotImplementedError("the MFM fusion is on the hot path as a frozen feature extractor: call .eval()")
+        self.check_features(mods[0])
         N, L, d = mods[0].shape
         D = d * self.n_mod
         cat = torch.empty((N * L, D), dtype=torch.float32, device=mods[0].device)

@@ -70,6 +70,10 @@ def args_check(parser, args):
         parser.error("--checkpoint_dir is needed unless --no_save")
     if args.resume_from_checkpoint and args.checkpoint_dir is None:
         parser.error("--resume_from_checkpoint reads <checkpoint_dir>/checkpoint.pt")
+    if not 1 <= args.seq_len <= ops.MFM_MAX_L:
+        parser.error("--seq_len %d: the fusions take clips of 1 to %d frames" % (args.seq_len, ops.MFM_MAX_L))
+    if not args.shirt_num < args.seq_len:
+        parser.error("--shirt_num %d must be below --seq_len %d" % (args.shirt_num, args.seq_len))
     args.trans_linear_in_dim = 2048
     args.query_per_class_test = args.query_per_class
     return args
