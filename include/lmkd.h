@@ -231,6 +231,11 @@ int lmkd_jpeg_decode(const unsigned char* data, const void* descs, const void* p
 /* the same routines on the CPU, every pointer HOST memory (the tests' reference; not on the training path) */
 int lmkd_jpeg_decode_host(const unsigned char* data, const void* descs, const void* pool, int n, short* coef, unsigned char* planes,
                           unsigned char* out, int* status);
+/* lmkd_jpeg_decode_host with the entropy stage run by the entropy launch's own program (csrc/jpeg_core.h entropy_windowed: the 8 KiB
+ * window with its refill rule, the 48-block staging area and its flush to coef), the 64 lanes of the wave run in turn on the CPU; the
+ * window and the staging area are heap blocks of exactly the kernel's sizes.  Same arguments, same results. */
+int lmkd_jpeg_decode_host_windowed(const unsigned char* data, const void* descs, const void* pool, int n, short* coef,
+                                   unsigned char* planes, unsigned char* out, int* status);
 /* ---- PNG frames (teacher/code/AuxDataset.py:129-136 read_single_image = Image.open(path).convert("RGB") over os.listdir of a video
  * folder; teacher/code/video_reader.py:190-199 the same on the teacher's episode reader), csrc/png.hip + csrc/png_core.h.  The GPU decodes
  * non-interlaced 8-bit images of colour type 0 (gray), 2 (RGB), 3 (palette) and 6 (RGBA) into uint8 [H][W][3] equal to PIL's

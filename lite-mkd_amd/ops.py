@@ -1668,13 +1668,16 @@ def _pil_decode(data, name, convert_rgb=False, label="JPEG"):
     import io
     import numpy as np
     from PIL import Image
-    with Image.open(io.BytesIO(data)) as im:
-        im.load()
-        if im.mode != "RGB":
-            if not convert_rgb:
-                raise ValueError("%s %s: PIL decodes it as mode %s, the frame transform takes RGB" % (label, name, im.mode))
-            return np.array(im.convert("RGB"))
-        return np.array(im)
+    try:
+        with Image.open(io.BytesIO(data)) as im:
+            im.load()
+            if im.mode != "RGB":
+                if not convert_rgb:
+                    raise ValueError("%s %s: PIL decodes it as mode %s, the frame transform takes RGB" % (label, name, im.mode))
+                return np.array(im.convert("RGB"))
+            return np.array(im)
+    except (OSError, SyntaxError) as e:      # damage in a file the plan leaves to PIL: named like every other damaged image
+        raise ValueError("%s %s is malformed: PIL refuses it: %s" % (label, name, e)) from e
 
 
 class JpegPlan:
@@ -1836,20 +1839,22 @@ def jpeg_decode(blobs, out=None, offsets=None, names=None, check=True):
     return plan.decode(out=out, check=check)
 
 
-def jpeg_decode_host(blobs):
+def jpeg_decode_host(blobs, windowed=False, fallback=True):
     """lmkd_jpeg_decode_host: the device routines run on the CPU (the tests' reference) -> (list of uint8 [H, W, 3] numpy arrays,
-    None for images the plan does not decode on the GPU; the plan; status per image)"""
+    None for images the plan does not decode on the GPU; the plan; status per image).  windowed: lmkd_jpeg_decode_host_windowed, the
+    entropy launch's own program (window, refill, staging, flush) with the wave's lanes run in turn.  fallback=False builds the plan
+    without the PIL decode of the unsupported images (a batch of damaged files)."""
     import numpy as np
-    plan = JpegPlan(blobs, pin=False)
+    plan = JpegPlan(blobs, pin=False, fallback=fallback)
     blocks = int(plan.totals[1])
-    coef = np.zeros(max(1, blocks * 64), dtype=np.int16)
+    coef = torch.zeros(max(64, blocks * 64), dtype=torch.int16).numpy()      # (torch aligns its host buffers to 64 bytes)
     planes = np.zeros(max(1, blocks * 64), dtype=np.uint8)
     out = np.zeros(max(1, int(plan.totals[2])), dtype=np.uint8)
     status = np.zeros(plan.n, dtype=np.int32)
     base = plan.buf.data_ptr()
     P = lambda a: ctypes.c_void_p(a.ctypes.data)      # noqa: E731
-    lib().call("lmkd_jpeg_decode_host", ctypes.c_void_p(base + plan.data_off), ctypes.c_void_p(base), ctypes.c_void_p(base + plan.pool_off),
-               plan.n, P(coef), P(planes), P(out), P(status))
+    lib().call("lmkd_jpeg_decode_host_windowed" if windowed else "lmkd_jpeg_decode_host", ctypes.c_void_p(base + plan.data_off),
+               ctypes.c_void_p(base), ctypes.c_void_p(base + plan.pool_off), plan.n, P(coef), P(planes), P(out), P(status))
     imgs = []
     for i, (h, w) in enumerate(plan.shapes()):
         o = int(plan.info[i, 4])

@@ -4,10 +4,14 @@ trainloop.StreamedEpisodes), the --rgb_path command lines, and no train / test m
 import io
 import os
 import random
+import sys
 
 import numpy as np
 import pytest
 import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _jpeg_util as U  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -52,21 +56,51 @@ def test_fixtures_one_mixed_batch_bit_exact(dev):
 
 
 def test_altered_scan_is_malformed_and_isolated(dev):
+    """Damaged streams of the host corruption matrix (tests/_jpeg_util.py; every one of them has been through
+    tools/jpeg_host_check.cpp) between good images, in one batch: an EOI planted half way, one case per status word 1..5, and four
+    321x239 cases damaged beyond the first 8 KiB window (two the host twin flags, two it does not).  The GPU gives the host twin's
+    status list, the good images bit for bit, the host twin's pixels for the unflagged damaged ones, and the same bits twice."""
     from litemkd_amd import ops
-    fx = [f for f in _fixtures() if f[0] in ("53x37_ss2_q75", "53x37_ss1_q95", "53x37_ss0_restart_marker_rows")]
-    base = fx[0][1]
-    sos = base.index(b"\xff\xda")
-    mid = (sos + len(base)) // 2
-    bad = base[:mid] + b"\xff\xd9" + base[mid + 2:]
-    blobs = [fx[1][1], bad, fx[2][1]]
+    good = [U.fixture(n) for n in ("53x37_ss1_q95", "53x37_ss0_restart_marker_rows", "320x240_ss2_q75")]
+    cases = U.full_matrix() + [U.renumbered_rst()]
+    _, hplan, hs = ops.jpeg_decode_host([c[1] for c in cases], fallback=False)
+    pick, deep = {}, {True: [], False: []}
+    for (label, data), (v, _), s in zip(cases, hplan.verdicts(), hs.tolist()):
+        if v != ops.JPEG_SUPPORTED:
+            continue
+        if s not in pick and (s == 3 if "cut@" in label else s == 4 if "rst@" in label else s in (1, 2, 5)):
+            pick[s] = (label, data)
+        if label.startswith("321x239") and "flip@" in label and U.offset_of(label) > 8192 and len(deep[s != 0]) < 2:
+            deep[s != 0].append((label, data))
+    assert sorted(pick) == [1, 2, 3, 4, 5] and len(deep[True]) == 2 and len(deep[False]) == 2, (sorted(pick), deep)
+    blobs = ([good[0][1], U.planted_eoi()[1]] + [pick[s][1] for s in (1, 2, 3, 4, 5)] + [good[1][1]]
+             + [c[1] for c in deep[True] + deep[False]] + [good[2][1]])
+    names = ["g0.jpg", "eoi.jpg", "s1.jpg", "s2.jpg", "s3.jpg", "s4.jpg", "s5.jpg", "g1.jpg", "deep_f0.jpg", "deep_f1.jpg", "deep_u0.jpg",
+             "deep_u1.jpg", "g2.jpg"]
+    himgs, _, hstatus = ops.jpeg_decode_host(blobs, fallback=False)
+    assert hstatus.tolist()[2:7] == [1, 2, 3, 4, 5] and hstatus.tolist()[10:] == [0, 0, 0] and all(hstatus.tolist()[8:10])
     frames, status = ops.jpeg_decode(blobs, check=False)
     st = status.cpu().tolist()
-    assert st[0] == 0 and st[1] != 0 and st[2] == 0
-    assert np.array_equal(frames[0].cpu().numpy(), fx[1][2]) and np.array_equal(frames[2].cpu().numpy(), fx[2][2])
+    assert st == hstatus.tolist(), (st, hstatus.tolist())
+    assert st[0] == 0 and st[1] != 0 and st[7] == 0 and st[12] == 0
+    first = [f.cpu().numpy() for f in frames]
+    for k, g in zip((0, 7, 12), good):
+        assert np.array_equal(first[k], g[2]), g[0]
+    for k in (10, 11):                                   # damaged, not flagged: whatever libjpeg makes of them, the host twin's pixels
+        assert np.array_equal(first[k], himgs[k]), names[k]
+        assert not np.array_equal(first[k], U.fixture("321x239_ss1_q90_rows")[2]), names[k]
+    frames2, status2 = ops.jpeg_decode(blobs, check=False)
+    # the same bits twice, the stopped images included: the blocks a stopped image never wrote keep what the scratch held, and the two
+    # decodes share the scratch of this (device, stream) with nothing in between
+    assert status2.cpu().tolist() == st
+    assert all(np.array_equal(a, b.cpu().numpy()) for a, b in zip(first, frames2)), [n for n, a, b in zip(names, first, frames2)
+                                                                                    if not np.array_equal(a, b.cpu().numpy())]
+    with pytest.raises(ValueError, match=r"JPEG image 1 \(eoi\.jpg\) is malformed"):
+        ops.jpeg_decode(blobs, names=names)
     with pytest.raises(ValueError, match="image 1"):
         ops.jpeg_decode(blobs)
     with pytest.raises(ValueError, match="image 0 .*malformed"):
-        ops.jpeg_decode([base[:40]])
+        ops.jpeg_decode([good[0][1][:40]])
 
 
 def _frame(value, g, h=100, w=132):

@@ -1,45 +1,21 @@
-"""CPU: the JPEG plan's verdicts (csrc/jpeg.hip lmkd_jpeg_plan), the device routines run on the host (lmkd_jpeg_decode_host) against
-PIL's decode (tests/golden/jpeg/fixtures.npz, tools/gen_jpeg_golden.py), and the dataset side of train.JpegFrameEpisodes: the index of
-a frame directory and of its .zip, split-list filtering (video_reader.py:305-319 _select_fold), teacher features matched by name."""
+"""CPU: the JPEG plan's verdicts (csrc/jpeg.hip lmkd_jpeg_plan), the device routines run on the host (lmkd_jpeg_decode_host, and
+lmkd_jpeg_decode_host_windowed: the entropy kernel's own windowed program, csrc/jpeg_core.h) against PIL's decode
+(tests/golden/jpeg/fixtures.npz, tools/gen_jpeg_golden.py; a corruption matrix, tests/_jpeg_util.py), and the dataset side of
+train.JpegFrameEpisodes: the index of a frame directory and of its .zip, split-list filtering (video_reader.py:305-319 _select_fold),
+teacher features matched by name."""
 import io
 import os
 import random
+import sys
 import zipfile
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FIXTURES = os.path.join(ROOT, "tests", "golden", "jpeg", "fixtures.npz")
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _jpeg_util as U  # noqa: E402
 
-
-def _fixtures():
-    z = np.load(FIXTURES)
-    return [(str(n), z["jpg_%d" % i].tobytes(), (np.cumsum(z["rgbd_%d" % i].astype(np.int64), axis=1) % 256).astype(np.uint8))
-            for i, n in enumerate(z["names"])]
-
-
-def _segments(data):
-    """a JPEG file -> [(marker, payload)] up to and including SOS, then ("scan", rest of the file)"""
-    out, pos = [], 2
-    while True:
-        m = data[pos + 1]
-        L = (data[pos + 2] << 8) | data[pos + 3]
-        out.append((m, bytearray(data[pos + 4:pos + 2 + L])))
-        pos += 2 + L
-        if m == 0xDA:
-            out.append(("scan", bytearray(data[pos:])))
-            return out
-
-
-def _join(segs):
-    b = bytearray(b"\xff\xd8")
-    for m, p in segs:
-        if m == "scan":
-            b += p
-        else:
-            b += bytes([0xFF, m, (len(p) + 2) >> 8, (len(p) + 2) & 255]) + p
-    return bytes(b)
+_fixtures, _segments, _join = U.fixtures, U.segments, U.join
 
 
 def _baseline():
@@ -165,6 +141,105 @@ def test_host_decode_flags_altered_scan():
     assert status[0] == 0 and status[1] != 0 and status[2] == 0
     with pytest.raises(ValueError, match="image 1"):
         plan.raise_on_status(status)
+
+
+def test_corruption_matrix():
+    """One altered byte at seeded positions of the scan, and scans cut short with an EOI appended (U.MATRIX: 1 615 flips, 35 cuts),
+    through the flat host twin and through the entropy launch's own windowed program run lane by lane.  JPEG has no checksum: a flip
+    that leaves the Huffman stream decodable to the right number of blocks is not flagged (13 % to 79 % of the flips of a fixture,
+    55 % over the matrix), so an unflagged case has to decode to exactly what libjpeg decodes with its C IDCT (jidctint.c)."""
+    from litemkd_amd import ops
+    cases = U.full_matrix()
+    rst = U.renumbered_rst()
+    good = U.fixture("53x37_ss1_q95")
+    blobs = [c[1] for c in cases] + [rst[1], good[1]]
+    imgs, plan, status = ops.jpeg_decode_host(blobs, fallback=False)
+    wimgs, wplan, wstatus = ops.jpeg_decode_host(blobs, windowed=True, fallback=False)
+    verdicts = plan.verdicts()
+    assert wplan.verdicts() == verdicts
+    # the windowed twin: the flat twin's status on every case, its pixels wherever the status is 0
+    assert wstatus.tolist() == status.tolist(), [(c[0], int(a), int(b)) for c, a, b in zip(cases, status, wstatus) if a != b][:10]
+    for k, (a, b, s) in enumerate(zip(imgs, wimgs, status)):
+        if a is not None and s == 0:
+            assert np.array_equal(a, b), k
+    # the good image is untouched
+    assert verdicts[-1] == (ops.JPEG_SUPPORTED, "supported") and status[-1] == 0
+    assert np.array_equal(imgs[-1], good[2]) and np.array_equal(wimgs[-1], good[2])
+    # the renumbered RST
+    assert verdicts[-2][0] == ops.JPEG_SUPPORTED and status[-2] == 4, (verdicts[-2], status[-2])
+    seen, unflagged, deep = {}, [], 0
+    for k, ((label, data), (v, why), s) in enumerate(zip(cases, verdicts, status.tolist())):
+        assert v in (ops.JPEG_SUPPORTED, ops.JPEG_MALFORMED) or (v, why) == (ops.JPEG_UNSUPPORTED, "more than one scan"), (label, v, why)
+        if label.startswith("321x239") and "flip@" in label and U.offset_of(label) > 8192:
+            deep += 1
+        if v != ops.JPEG_SUPPORTED:
+            assert s == 0, label
+            seen["plan"] = seen.get("plan", 0) + 1
+        elif s:
+            assert 1 <= s <= 5, (label, s)          # 6 would be the decoder leaving its own window
+            seen[s] = seen.get(s, 0) + 1
+        else:
+            unflagged.append(k)
+        if "cut@" in label:
+            assert v == ops.JPEG_SUPPORTED and s == 3, (label, v, s)      # a cut scan ends early
+    print("corruption matrix: %d cases, flagged %s, unflagged %d, beyond the first window %d" % (len(cases), seen, len(unflagged), deep))
+    assert {1, 2, 3, 5} <= set(seen), seen
+    flagged = len(cases) - len(unflagged)
+    assert 4 * flagged >= len(cases), (flagged, len(cases))          # not vacuous: at least 25 % flagged ...
+    assert len(unflagged) >= 500, len(unflagged)                     # ... and at least 500 compared with libjpeg
+    assert deep >= 50, deep                                          # the refill path under damage
+    refs = U.pil_rgb_c_idct([cases[k][1] for k in unflagged])
+    refused = [cases[k][0] for k, r in zip(unflagged, refs) if r is None]
+    assert not refused, refused[:10]
+    for k, ref in zip(unflagged, refs):
+        assert imgs[k].shape == ref.shape and np.array_equal(imgs[k], ref), (cases[k][0], int((imgs[k] != ref).sum()))
+
+
+def test_unsupported_image_that_pil_refuses_is_named():
+    """a flip that plants a marker inside the scan makes the plan's verdict 'unsupported: more than one scan'; the image goes to PIL,
+    and where PIL refuses it too the error is the ValueError every other damaged image raises, naming the image"""
+    from PIL import Image
+    from litemkd_amd import ops
+    import _png_util as PU
+    cases = U.corruption_matrix("53x37_ss2_q75", flips=300, seed=0)
+    plan = ops.JpegPlan([c[1] for c in cases], pin=False, fallback=False)
+    un = [k for k, (v, why) in enumerate(plan.verdicts()) if v == ops.JPEG_UNSUPPORTED]
+    assert len(un) == 3 and all(plan.verdicts()[k][1] == "more than one scan" for k in un)
+
+    def pil_error(data):
+        try:
+            with Image.open(io.BytesIO(data)) as im:
+                im.load()
+        except OSError as e:
+            return e
+        return None
+    errors = {k: pil_error(cases[k][1]) for k in un}
+    refused = [k for k in un if errors[k] is not None]
+    assert refused, "PIL decodes all three"
+    good = _baseline()
+    for k in un:
+        blobs, names = [good, cases[k][1], good], ["a.jpg", "b.jpg", "c.jpg"]
+        if errors[k] is None:
+            p = ops.JpegPlan(blobs, names=names, pin=False)
+            assert sorted(p.fallback) == [1] and p.fallback[1].shape == (37, 53, 3)
+            continue
+        with pytest.raises(ValueError) as ei:
+            ops.JpegPlan(blobs, names=names, pin=False)
+        assert "JPEG image 1 (b.jpg) is malformed" in str(ei.value) and str(errors[k]) in str(ei.value), str(ei.value)
+        assert isinstance(ei.value.__cause__, OSError) and str(ei.value.__cause__) == str(errors[k])
+        with pytest.raises(ValueError, match=r"JPEG image 1 is malformed: PIL refuses it"):
+            ops.jpeg_decode_host(blobs)
+    # PngPlan shares the fallback: an interlaced file (unsupported) whose stream is cut short
+    lace = PU.fixture("17x9_interlaced")[1]
+    z = PU.stream_of(lace)
+    cut = PU.with_stream(lace, z[:len(z) // 2])
+    assert ops.PngPlan([cut], pin=False, fallback=False).verdicts()[0] == (ops.PNG_UNSUPPORTED, "Adam7 interlace")
+    err = pil_error(cut)
+    assert err is not None
+    with pytest.raises(ValueError) as ei:
+        ops.PngPlan([PU.fixture("53x37_t2_mix")[1], cut], names=["a.png", "b.png"], pin=False)
+    assert "PNG image 1 (b.png) is malformed" in str(ei.value) and str(err) in str(ei.value), str(ei.value)
+    assert isinstance(ei.value.__cause__, OSError)
 
 
 def _tree(root, classes=3, videos=3, frames=9, short=None):

@@ -2,6 +2,7 @@
 (PIL.Image.open(f).load(), the reference's read_single_image, video_reader.py:334-343) - the expected output of ops.jpeg_decode.
 
     python tools/gen_jpeg_golden.py
+    python tools/gen_jpeg_golden.py --dump DIR      (writes the committed fixtures out as DIR/<name>.jpg)
 
 The matrix: 4:4:4 / 4:2:2 / 4:2:0, qualities 50 / 75 / 95 and optimize=True, restart_marker_blocks=3 and restart_marker_rows=1, sizes
 320x240, 321x239, 53x37, 17x9 and 1..4 pixels wide or high, and one progressive file (the host fallback).  Keys: "names" (one string
@@ -83,5 +84,16 @@ def main(path=os.path.join(ROOT, "tests", "golden", "jpeg", "fixtures.npz")):
     print("%s: %d fixtures, %d bytes" % (path, len(names), os.path.getsize(path)))
 
 
+def dump(directory):
+    """the files of the committed fixtures as <directory>/<name>.jpg (the input of tools/jpeg_host_check.cpp)"""
+    os.makedirs(directory, exist_ok=True)
+    for name, data, _ in load_fixtures():
+        with open(os.path.join(directory, name + ".jpg"), "wb") as f:
+            f.write(data)
+
+
 if __name__ == "__main__":
-    main(*sys.argv[1:])
+    if sys.argv[1:2] == ["--dump"]:
+        dump(sys.argv[2])
+    else:
+        main(*sys.argv[1:])
