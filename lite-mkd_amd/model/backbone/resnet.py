@@ -33,6 +33,19 @@ class _BN(nn.Module):
         return self.weight, self.bias, self.running_mean, self.running_var
 
 
+def _res_block(blk, x, seg, *stages):
+    """one ops.ResBlockFn node over the block's (conv, bn) chain stages and its downsample (None x 5 when absent)"""
+    if blk.downsample is not None:
+        stages += ((blk.downsample[0], blk.downsample[1]),)
+    params = []
+    for conv, bn in stages:
+        ops.mark_cacheable(conv.weight)
+        params += [conv.weight, *bn.args()]
+    if blk.downsample is None:
+        params += [None] * 5
+    return ops.ResBlockFn.apply(x, blk.stride, blk.training, seg, *params)
+
+
 class _Block(nn.Module):
     def __init__(self, cin, cout, stride):
         super().__init__()
@@ -49,16 +62,7 @@ class _Block(nn.Module):
 
     def forward(self, x, seg=0):
         """seg = F0 > 0: x holds both trunk calls of an episode, frames [0, F0) | [F0, F) (merged_trunk_call)"""
-        tr = self.training
-        ops.mark_cacheable(self.conv1.weight)
-        ops.mark_cacheable(self.conv2.weight)
-        if self.downsample is not None:
-            ops.mark_cacheable(self.downsample[0].weight)
-            ds = (self.downsample[0].weight,) + self.downsample[1].args()
-        else:
-            ds = (None, None, None, None, None)
-        return ops.BasicBlockFn.apply(x, self.stride, tr, self.conv1.weight, *self.bn1.args(),
-                                      self.conv2.weight, *self.bn2.args(), *ds, seg)
+        return _res_block(self, x, seg, (self.conv1, self.bn1), (self.conv2, self.bn2))
 
 
 class _Bottleneck(nn.Module):
@@ -81,15 +85,7 @@ class _Bottleneck(nn.Module):
             self.downsample.add_module("1", _BN(cout))
 
     def forward(self, x, seg=0):
-        for c in (self.conv1, self.conv2, self.conv3):
-            ops.mark_cacheable(c.weight)
-        if self.downsample is not None:
-            ops.mark_cacheable(self.downsample[0].weight)
-            ds = (self.downsample[0].weight,) + self.downsample[1].args()
-        else:
-            ds = (None, None, None, None, None)
-        return ops.BottleneckFn.apply(x, self.stride, self.training, self.conv1.weight, *self.bn1.args(),
-                                      self.conv2.weight, *self.bn2.args(), self.conv3.weight, *self.bn3.args(), *ds, seg)
+        return _res_block(self, x, seg, (self.conv1, self.bn1), (self.conv2, self.bn2), (self.conv3, self.bn3))
 
 
 class ResNet18Trunk(nn.Module):

@@ -2057,7 +2057,7 @@ def image_decode(blobs, out=None, names=None, check=True, convert_rgb=False):
 GRAD_READY_HOOK = None
 
 
-# Test aid: with BLOCK_TAPS set to a list, every BasicBlockFn / BottleneckFn / StemFn training forward appends its BatchNorm inputs and
+# Test aid: with BLOCK_TAPS set to a list, every ResBlockFn / StemFn training forward appends its BatchNorm inputs and
 # statistics, so a test can reproduce the exact ReLU masks the HIP backward uses (mask flips at pre-activations within fp32
 # rounding of zero are the one legitimate source of percent-level gradient differences between two fp32 implementations).
 BLOCK_TAPS = None
@@ -2081,54 +2081,74 @@ def split_block_taps(taps):
     return calls[0] + calls[1]
 
 
-class BasicBlockFn(torch.autograd.Function):
-    """torchvision BasicBlock: conv3x3-BN-ReLU-conv3x3-BN (+1x1/2 conv-BN downsample) + add + ReLU.
-    One autograd node per block; backward is hand-scheduled so that the masked gradient buffer
-    of the residual branch is reused as the block-input gradient accumulator."""
+def _amax_carriers(x, chain):
+    """the saved tensors of a block that carry fp32h2 maxima into its backward: x, the stored activations, the raw outputs (inner stages)"""
+    return [x] + [s[4] for s in chain[:-1]] + [s[2] for s in chain[:-1]]
+
+
+class ResBlockFn(torch.autograd.Function):
+    """torchvision residual block as a chain of conv-BN(-ReLU) stages: BasicBlock (conv3x3/s - conv3x3) or Bottleneck (ResNet-50, v1.5:
+    conv1x1 - conv3x3/s - conv1x1), (+ conv1x1/s-BN downsample) + add + ReLU.  One autograd node per block; backward is hand-scheduled so
+    that the masked gradient buffer of the residual branch is reused as the block-input gradient accumulator."""
 
     @staticmethod
-    def forward(ctx, x, stride, training, w1, g1, b1, rm1, rv1, w2, g2, b2, rm2, rv2, wd, gd, bd, rmd, rvd, seg=0):
-        """seg = F0 > 0: frames [0, F0) | [F0, F) of x are the two trunk calls of an episode - one launch per kernel for both, per-segment
+    def forward(ctx, x, stride, training, seg, *params):
+        """params: (w, gamma, beta, running_mean, running_var) of each of the 2 or 3 chain stages, then of the downsample (None x 5 when
+        absent); kernel size and padding come from the weights, the stride sits on the first 3x3 stage and on the downsample.
+        seg = F0 > 0: frames [0, F0) | [F0, F) of x are the two trunk calls of an episode - one launch per kernel for both, per-segment
         BatchNorm statistics ([2, 5, C] tables), bit-identical activations and activation gradients to two calls"""
-        _chk(x, w1, w2, wd)
-        Cs = x.shape[-1]
+        n = len(params) // 5 - 1
+        stages = [params[5 * i:5 * i + 5] for i in range(n)]
+        wd, gd, bd, rmd, rvd = params[5 * n:]
+        strides = [stride if i == n - 2 else 1 for i in range(n)]
+        _chk(x, *[s[0] for s in stages], wd)
         if not training and _eval_fused():
             ctx.training = False
-            a1 = conv_bn_eval(x, w1, Cs, stride, 1, g1, b1, rm1, rv1, True)
-            r = x if wd is None else conv_bn_eval(x, wd, Cs, stride, 0, gd, bd, rmd, rvd, False, feeds_conv=False)
-            return conv_bn_eval(a1, w2, w1.shape[0], 1, 1, g2, b2, rm2, rv2, True, r)
+            h = x
+            for (w, g, b, rm, rv), s in zip(stages[:-1], strides):
+                h = conv_bn_eval(h, w, h.shape[-1], s, w.shape[2] // 2, g, b, rm, rv, True)
+            r = x if wd is None else conv_bn_eval(x, wd, x.shape[-1], stride, 0, gd, bd, rmd, rvd, False, feeds_conv=False)
+            w, g, b, rm, rv = stages[-1]
+            return conv_bn_eval(h, w, h.shape[-1], strides[-1], w.shape[2] // 2, g, b, rm, rv, True, r)
         fused = training and _train_fused()
         pre = training and _train_pre()
+        if n == 3:
+            # fp32h2: the 3x3 convolution's raw input c1 comes from a 1x1 convolution (a gather kernel: no maximum in its epilogue, a reduction
+            # pass instead); materialising relu(bn1(c1)) - whose BatchNorm-apply records the maximum for free - is faster here (ResNet-50 + MFM:
+            # 12.4 against 11.9 episodes/s), so the Bottleneck keeps the loader-side BatchNorm for the other arithmetics only
+            pre = pre and not (os.environ.get("LMKD_R50_PRE_H2", "0") != "1" and _h2_mode())
         seg = _seg_frames(seg, x.shape[0]) if training else 0
-        c1, st1 = _conv_bn_train_or_eval(x, w1, Cs, stride, 1, g1, b1, rm1, rv1, training, seg=seg, bound=pre)
-        if pre:         # conv2 normalises + rectifies c1 in its loader: a1 = relu(bn1(c1)) is never stored
-            a1 = None
-            c2, st2 = _conv_bn_train_or_eval(c1, w2, w1.shape[0], 1, 1, g2, b2, rm2, rv2, training, pre_stats=st1, seg=seg)
-        else:
-            a1 = bn_apply(c1, st1, True, seg=seg, site=("a", g1.data_ptr()))
-            c2, st2 = _conv_bn_train_or_eval(a1, w2, w1.shape[0], 1, 1, g2, b2, rm2, rv2, training, seg=seg)
+        h, hst, chain = x, None, []      # chain: (w, gamma, c, st, a) per stage, what the backward needs
+        for i, ((w, g, b, rm, rv), s) in enumerate(zip(stages, strides)):
+            # (only the first stage's output asks for the fp32h2 bound of its loader-side BatchNorm)
+            c, st = _conv_bn_train_or_eval(h, w, h.shape[-1], s, w.shape[2] // 2, g, b, rm, rv, training, pre_stats=hst, seg=seg, bound=pre and i == 0)
+            a = None
+            if i < n - 1 and pre:         # the next convolution normalises + rectifies c in its loader: a = relu(bn(c)) is never stored
+                h, hst = c, st
+            elif i < n - 1:
+                h = a = bn_apply(c, st, True, seg=seg, site=("a", g.data_ptr()))
+            chain.append((w, g, c, st, a))
         if wd is not None:
-            cd, std = _conv_bn_train_or_eval(x, wd, Cs, stride, 0, gd, bd, rmd, rvd, training, seg=seg)
+            cd, std = _conv_bn_train_or_eval(x, wd, x.shape[-1], stride, 0, gd, bd, rmd, rvd, training, seg=seg)
             res, rst = cd, std
         else:
             cd = std = None
             res, rst = x, None
         if fused:
-            y, ybits = bn_apply(c2, st2, True, res, rst, want_bits=True, seg=seg, site=("y", g2.data_ptr()))
+            y, ybits = bn_apply(c, st, True, res, rst, want_bits=True, seg=seg, site=("y", g.data_ptr()))
         else:
-            y, ybits = bn_apply(c2, st2, True, res, rst, seg=seg, site=("y", g2.data_ptr())), None
-        ctx.training = training
-        ctx.seg = seg
-        ctx.stride = stride
-        ctx.has_ds = wd is not None
-        ctx.fused = fused
-        ctx.betas = (b1, b2, bd)      # BatchNorm biases: the backward may add their gradients straight into .grad (DIRECT_PARAM_GRAD)
-        if BLOCK_TAPS is not None:
-            BLOCK_TAPS.append({"c1": c1, "st1": st1, "y": y, "seg": seg})
+            y, ybits = bn_apply(c, st, True, res, rst, seg=seg, site=("y", g.data_ptr())), None
+        ctx.training, ctx.seg, ctx.stride, ctx.strides, ctx.has_ds, ctx.fused = training, seg, stride, strides, wd is not None, fused
+        ctx.betas = tuple(s[2] for s in stages) + (bd,)      # BatchNorm biases: the backward may add their gradients straight into .grad (DIRECT_PARAM_GRAD)
         if training:
-            # fused: the backward needs neither a1 (recomputed from c1 in the weight-gradient loader) nor y (its mask travels as bits)
-            ctx.save_for_backward(x, w1, g1, c1, st1, a1, w2, g2, c2, st2, ybits if fused else y, wd, gd, cd, std)
-            ctx.amax = (_amax_tag(x), _amax_tag(a1), _amax_tag(c1))
+            if BLOCK_TAPS is not None:      # c{i} / st{i}: the raw convolution outputs of the inner stages in both forms (pre and materialised)
+                tap = {}
+                for i, s in enumerate(chain[:-1], 1):
+                    tap["c%d" % i], tap["st%d" % i] = s[2], s[3]
+                BLOCK_TAPS.append({**tap, "y": y, "seg": seg})
+            # fused: the backward needs neither a (recomputed from c in the weight-gradient loader) nor y (its mask travels as bits)
+            ctx.save_for_backward(x, ybits if fused else y, *[t for s in chain for t in s], wd, gd, cd, std)
+            ctx.amax = tuple(_amax_tag(t) for t in _amax_carriers(x, chain))
         return y
 
     @staticmethod
@@ -2136,131 +2156,47 @@ class BasicBlockFn(torch.autograd.Function):
         _audit.engine_owned(dy)
         if not ctx.training:
             raise NotImplementedError("backward through eval-mode BatchNorm is not part of the hot path")
-        x, w1, g1, c1, st1, a1, w2, g2, c2, st2, y, wd, gd, cd, std = ctx.saved_tensors
-        for t, tag in zip((x, a1, c1), ctx.amax):      # the maxima recorded in the forward (saved tensors may come back as new objects)
+        x, y, *saved = ctx.saved_tensors
+        wd, gd, cd, std = saved[-4:]
+        chain = [saved[i:i + 5] for i in range(0, len(saved) - 4, 5)]      # (w, gamma, c, st, a) per stage
+        n = len(chain)
+        for t, tag in zip(_amax_carriers(x, chain), ctx.amax):      # the maxima recorded in the forward (saved tensors may come back as new objects)
             _amax_retag(t, tag)
         dy = dy.contiguous()
-        stride = ctx.stride
-        seg = ctx.seg
-        Cmid = w1.shape[0]
-        # bn2 (+ReLU mask from y, or from its bits); g = masked dy = gradient of both residual branches
-        dc2, g, dg2, db2 = bn_backward(dy, c2, y, st2, g2, 3 if ctx.fused else 1, want_g=True, beta=ctx.betas[1], seg=seg)
-        wd2 = pack_weights(w2, Cmid, 1)
-        # first: its stream then waits for the BatchNorm backward only, not for the data gradient
-        dw2 = weight_grad(w2, c1, dc2, 1, 1, st1, seg=seg) if a1 is None else weight_grad(w2, a1, dc2, 1, 1, seg=seg)
-        da1, part1 = conv_bwd_data(dc2, wd2, c1.shape, Cmid, 3, 3, 1, 1, bn=(c1, st1), seg=seg)      # + bn1's backward sums where the launch has the form
-        del dc2
-        dc1, _, dg1, db1 = bn_backward(da1, c1, None, st1, g1, 2, dx_out=da1, beta=ctx.betas[0], part=part1, seg=seg)    # mask from c1*scale+shift > 0
-        dw1 = weight_grad(w1, x, dc1, stride, 1, seg=seg)
+        stride, strides, seg = ctx.stride, ctx.strides, ctx.seg
+        grads = [None] * n      # (dw, dgamma, dbeta) per stage
+        # the last BatchNorm (+ReLU mask from y, or from its bits); g = masked dy = gradient of both residual branches
+        w, gam, c, st, _ = chain[-1]
+        dc, g, dg, db = bn_backward(dy, c, y, st, gam, 3 if ctx.fused else 1, want_g=True, beta=ctx.betas[n - 1], seg=seg)
+        for i in range(n - 1, 0, -1):      # dc: the gradient of stage i's raw output; (c, st, a, gam): its input, the output of stage i - 1
+            k = w.shape[2]
+            _, gam, c, st, a = chain[i - 1]
+            # weight gradient first: its stream then waits for the BatchNorm backward only, not for the data gradient
+            dw = weight_grad(w, c, dc, strides[i], k // 2, st, seg=seg) if a is None else weight_grad(w, a, dc, strides[i], k // 2, seg=seg)
+            grads[i] = (dw, dg, db)
+            da, part = conv_bwd_data(dc, pack_weights(w, w.shape[1], 1), c.shape, w.shape[0], k, k, strides[i], k // 2, bn=(c, st), seg=seg)      # + the BatchNorm's backward sums where the launch has the form
+            del dc
+            dc, _, dg, db = bn_backward(da, c, None, st, gam, 2, dx_out=da, beta=ctx.betas[i - 1], part=part, seg=seg)    # mask from c*scale+shift > 0
+            w = chain[i - 1][0]
+        k = w.shape[2]
+        grads[0] = (weight_grad(w, x, dc, strides[0], k // 2, seg=seg), dg, db)
         dwd = dgd = dbd = None
         need_dx = ctx.needs_input_grad[0]
         dx = None
         if ctx.has_ds:
-            dcd, _, dgd, dbd = bn_backward(g, cd, None, std, gd, 0, dx_out=g, beta=ctx.betas[2], seg=seg)
+            dcd, _, dgd, dbd = bn_backward(g, cd, None, std, gd, 0, dx_out=g, beta=ctx.betas[n], seg=seg)
             dwd = weight_grad(wd, x, dcd, stride, 0, seg=seg)
             if need_dx:
-                # the 3x3 gradient writes every input pixel; the 1x1 stride-2 one then accumulates onto the quarter of the
+                # the first stage's gradient writes every input pixel; the strided 1x1 one then accumulates onto the quarter of the
                 # pixels it reaches (parity classes without a tap launch nothing) instead of writing three quarters of zeros
-                dx = conv_bwd_data(dc1, pack_weights(w1, Cmid, 1), x.shape, Cmid, 3, 3, stride, 1, seg=seg)
-                conv_bwd_data(dcd, pack_weights(wd, Cmid, 1), x.shape, Cmid, 1, 1, stride, 0, out=dx, accumulate=True, seg=seg)
+                dx = conv_bwd_data(dc, pack_weights(w, w.shape[1], 1), x.shape, w.shape[0], k, k, strides[0], k // 2, seg=seg)
+                conv_bwd_data(dcd, pack_weights(wd, wd.shape[1], 1), x.shape, wd.shape[0], 1, 1, stride, 0, out=dx, accumulate=True, seg=seg)
         else:
             dx = g                                    # identity branch
             if need_dx:
-                conv_bwd_data(dc1, pack_weights(w1, Cmid, 1), x.shape, Cmid, 3, 3, stride, 1, out=dx, accumulate=True, seg=seg)   # dx += dgrad(conv1)
-        return (dx if need_dx else None, None, None, dw1, dg1, db1, None, None, dw2, dg2, db2, None, None,
-                dwd, dgd, dbd, None, None, None)
-
-
-class BottleneckFn(torch.autograd.Function):
-    """torchvision Bottleneck (ResNet-50, v1.5: the stride sits on the 3x3 conv): conv1x1-BN-ReLU-conv3x3/s-BN-ReLU-
-    conv1x1-BN (+ conv1x1/s-BN downsample) + add + ReLU.  Same hand-scheduled backward as BasicBlockFn."""
-
-    @staticmethod
-    def forward(ctx, x, stride, training, w1, g1, b1, rm1, rv1, w2, g2, b2, rm2, rv2, w3, g3, b3, rm3, rv3,
-                wd, gd, bd, rmd, rvd, seg=0):
-        _chk(x, w1, w2, w3, wd)
-        Cs = x.shape[-1]
-        Cm = w1.shape[0]
-        if not training and _eval_fused():
-            ctx.training = False
-            a1 = conv_bn_eval(x, w1, Cs, 1, 0, g1, b1, rm1, rv1, True)
-            a2 = conv_bn_eval(a1, w2, Cm, stride, 1, g2, b2, rm2, rv2, True)
-            r = x if wd is None else conv_bn_eval(x, wd, Cs, stride, 0, gd, bd, rmd, rvd, False, feeds_conv=False)
-            return conv_bn_eval(a2, w3, Cm, 1, 0, g3, b3, rm3, rv3, True, r)
-        fused = training and _train_fused()
-        # fp32h2: the 3x3 convolution's raw input c1 comes from a 1x1 convolution (a gather kernel: no maximum in its epilogue, a reduction
-        # pass instead); materialising relu(bn1(c1)) - whose BatchNorm-apply records the maximum for free - is faster here (ResNet-50 + MFM:
-        # 12.4 against 11.9 episodes/s), so the Bottleneck keeps the loader-side BatchNorm for the other arithmetics only
-        pre = training and _train_pre() and not (os.environ.get("LMKD_R50_PRE_H2", "0") != "1" and _h2_mode())
-        seg = _seg_frames(seg, x.shape[0]) if training else 0      # two frame segments (BasicBlockFn)
-        c1, st1 = _conv_bn_train_or_eval(x, w1, Cs, 1, 0, g1, b1, rm1, rv1, training, seg=seg, bound=pre)      # (c1 feeds the 3x3 convolution's loader)
-        if pre:         # conv2 / conv3 normalise + rectify their raw inputs in the loader (BasicBlockFn)
-            a1 = a2 = None
-            c2, st2 = _conv_bn_train_or_eval(c1, w2, Cm, stride, 1, g2, b2, rm2, rv2, training, pre_stats=st1, seg=seg)
-            c3, st3 = _conv_bn_train_or_eval(c2, w3, Cm, 1, 0, g3, b3, rm3, rv3, training, pre_stats=st2, seg=seg)
-        else:
-            a1 = bn_apply(c1, st1, True, seg=seg, site=("a", g1.data_ptr()))
-            c2, st2 = _conv_bn_train_or_eval(a1, w2, Cm, stride, 1, g2, b2, rm2, rv2, training, seg=seg)
-            a2 = bn_apply(c2, st2, True, seg=seg, site=("a", g2.data_ptr()))
-            c3, st3 = _conv_bn_train_or_eval(a2, w3, Cm, 1, 0, g3, b3, rm3, rv3, training, seg=seg)
-        if wd is not None:
-            cd, std = _conv_bn_train_or_eval(x, wd, Cs, stride, 0, gd, bd, rmd, rvd, training, seg=seg)
-            res, rst = cd, std
-        else:
-            cd = std = None
-            res, rst = x, None
-        if fused:
-            y, ybits = bn_apply(c3, st3, True, res, rst, want_bits=True, seg=seg, site=("y", g3.data_ptr()))
-        else:
-            y, ybits = bn_apply(c3, st3, True, res, rst, seg=seg, site=("y", g3.data_ptr())), None
-        ctx.training, ctx.stride, ctx.has_ds, ctx.fused = training, stride, wd is not None, fused
-        ctx.seg = seg
-        ctx.betas = (b1, b2, b3, bd)
-        if BLOCK_TAPS is not None and training:      # c1 / c2: the raw convolution outputs in both forms (pre and materialised)
-            BLOCK_TAPS.append({"c1": c1, "st1": st1, "c2": c2, "st2": st2, "y": y, "seg": seg})
-        if training:
-            ctx.save_for_backward(x, w1, g1, c1, st1, a1, w2, g2, c2, st2, a2, w3, g3, c3, st3, ybits if fused else y, wd, gd, cd, std)
-            ctx.amax = tuple(_amax_tag(t) for t in (x, a1, a2, c1, c2))
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        _audit.engine_owned(dy)
-        if not ctx.training:
-            raise NotImplementedError("backward through eval-mode BatchNorm is not part of the hot path")
-        x, w1, g1, c1, st1, a1, w2, g2, c2, st2, a2, w3, g3, c3, st3, y, wd, gd, cd, std = ctx.saved_tensors
-        for t, tag in zip((x, a1, a2, c1, c2), ctx.amax):
-            _amax_retag(t, tag)
-        dy = dy.contiguous()
-        stride = ctx.stride
-        fused = ctx.fused
-        seg = ctx.seg
-        Cm, Co = w1.shape[0], w3.shape[0]
-        dc3, g, dg3, db3 = bn_backward(dy, c3, y, st3, g3, 3 if fused else 1, want_g=True, beta=ctx.betas[2], seg=seg)
-        dw3 = weight_grad(w3, c2, dc3, 1, 0, st2, seg=seg) if a2 is None else weight_grad(w3, a2, dc3, 1, 0, seg=seg)       # weight gradients first (BasicBlockFn)
-        da2, part2 = conv_bwd_data(dc3, pack_weights(w3, Cm, 1), c2.shape, Co, 1, 1, 1, 0, bn=(c2, st2), seg=seg)
-        del dc3
-        dc2, _, dg2, db2 = bn_backward(da2, c2, None, st2, g2, 2, dx_out=da2, beta=ctx.betas[1], part=part2, seg=seg)
-        dw2 = weight_grad(w2, c1, dc2, stride, 1, st1, seg=seg) if a1 is None else weight_grad(w2, a1, dc2, stride, 1, seg=seg)
-        da1, part1 = conv_bwd_data(dc2, pack_weights(w2, Cm, 1), c1.shape, Cm, 3, 3, stride, 1, bn=(c1, st1), seg=seg)
-        del dc2, da2
-        dc1, _, dg1, db1 = bn_backward(da1, c1, None, st1, g1, 2, dx_out=da1, beta=ctx.betas[0], part=part1, seg=seg)
-        dw1 = weight_grad(w1, x, dc1, 1, 0, seg=seg)
-        dwd = dgd = dbd = None
-        need_dx = ctx.needs_input_grad[0]
-        dx = None
-        if ctx.has_ds:
-            dcd, _, dgd, dbd = bn_backward(g, cd, None, std, gd, 0, dx_out=g, beta=ctx.betas[3], seg=seg)
-            dwd = weight_grad(wd, x, dcd, stride, 0, seg=seg)
-            if need_dx:      # conv1's gradient first (writes every pixel), the strided downsample one accumulates (BasicBlockFn)
-                dx = conv_bwd_data(dc1, pack_weights(w1, x.shape[-1], 1), x.shape, Cm, 1, 1, 1, 0, seg=seg)
-                conv_bwd_data(dcd, pack_weights(wd, x.shape[-1], 1), x.shape, Co, 1, 1, stride, 0, out=dx, accumulate=True, seg=seg)
-        else:
-            dx = g
-            if need_dx:
-                conv_bwd_data(dc1, pack_weights(w1, x.shape[-1], 1), x.shape, Cm, 1, 1, 1, 0, out=dx, accumulate=True, seg=seg)
-        return (dx if need_dx else None, None, None, dw1, dg1, db1, None, None, dw2, dg2, db2, None, None,
-                dw3, dg3, db3, None, None, dwd, dgd, dbd, None, None, None)
+                conv_bwd_data(dc, pack_weights(w, w.shape[1], 1), x.shape, w.shape[0], k, k, strides[0], k // 2, out=dx, accumulate=True, seg=seg)   # dx += dgrad(first stage)
+        return (dx if need_dx else None, None, None, None, *[v for dw, dg, db in grads for v in (dw, dg, db, None, None)],
+                dwd, dgd, dbd, None, None)
 
 
 class PoolHeadFn(torch.autograd.Function):

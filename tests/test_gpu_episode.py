@@ -310,7 +310,7 @@ def _episode_matches_oracle(dev, shot, query, img, clf, dist, bb, bf16=False, tr
             # tests, where every mask is imposed, hold the 2e-6 floor at 200 frames in the same arithmetic)
             # (round 3, later: the pooling selections ARE imposed now for the BasicBlock trunks - _hip_pool_choices / oracle.POOL_HOOK -
             # so what remains there is a linear map; the ResNet-50 cases, whose masks and selections were not imposed then, kept 1e-4)
-            # (round 6: imposed for the Bottleneck trunks too - ops.BottleneckFn taps, oracle.resnet50_trunk through the hooks: the CPU pair
+            # (round 6: imposed for the Bottleneck trunks too - ops.ResBlockFn taps, oracle.resnet50_trunk through the hooks: the CPU pair
             # of the 64-px ResNet-50 episodes drops from 4e-3 ... 7e-3 to the 1e-5 class, so factor 3 binds there as well)
             e_hip, e_cpu = anchored(k, pg[k].grad, sp32[k].grad, sp64[k].grad, factor, 1e-4, 1e-7 * gmax)
             worst = max(worst, (e_hip / (e_cpu + 1e-6), k, e_hip, e_cpu))

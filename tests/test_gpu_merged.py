@@ -36,8 +36,23 @@ def _conv_w(co, ci, k, dev, g):
                                                       (1, 1, 28, 128, 128, 1),
                                                       (6, 2, 56, 64, 64, 1)])     # the widest halo (W = 56)
 def test_basic_block_two_segments_equal_two_calls(dev, mode, act, F0, F1, H, cin, cout, stride):
-    """ops.BasicBlockFn over [F0 + F1] frames with seg = F0 against two calls on the halves: block output, input gradient and the
+    """ops.ResBlockFn with two stages (BasicBlock), see _block_two_segments"""
+    _block_two_segments(dev, mode, act, F0, F1, H, cin, 0, cout, stride)
+
+
+@pytest.mark.parametrize("mode,act", [("fp32x3", "fp32"), ("fp32h2", "fp32"), ("bf16", "fp32"), ("bf16", "bf16")])
+@pytest.mark.parametrize("F0,F1,H,cin,mid,cout,stride", [(3, 5, 14, 64, 64, 256, 1),       # downsample at stride 1
+                                                          (3, 5, 14, 256, 64, 256, 1),      # identity
+                                                          (3, 5, 14, 256, 128, 512, 2)])    # downsample at stride 2: 3x3 stride 2 inside the block
+def test_bottleneck_two_segments_equal_two_calls(dev, mode, act, F0, F1, H, cin, mid, cout, stride):
+    """ops.ResBlockFn with three stages (Bottleneck: cin -> mid -> mid -> cout), see _block_two_segments"""
+    _block_two_segments(dev, mode, act, F0, F1, H, cin, mid, cout, stride)
+
+
+def _block_two_segments(dev, mode, act, F0, F1, H, cin, mid, cout, stride):
+    """ops.ResBlockFn over [F0 + F1] frames with seg = F0 against two calls on the halves: block output, input gradient and the
     deferred BatchNorm tables bit-identical; parameter gradients equal to the sum of the two calls' to fp32 rounding.
+    mid = 0: two 3x3 stages; else 1x1 (cin -> mid), 3x3 / stride, 1x1 (mid -> cout).
     fp32h2: the operand maxima are kept per frame segment, so the two-plane kernels scale each segment as its own launch would"""
     import litemkd_amd
     from litemkd_amd import ops
@@ -50,7 +65,11 @@ def test_basic_block_two_segments_equal_two_calls(dev, mode, act, F0, F1, H, cin
     x[F0:] *= 1.7                                   # the two calls get visibly different batch statistics
     x[F0:] += 0.3
     ds = stride != 1 or cin != cout
-    ps = [_conv_w(cout, cin, 3, dev, g), *_bn(cout, dev, g), _conv_w(cout, cout, 3, dev, g), *_bn(cout, dev, g)]
+    if mid:
+        ps = [_conv_w(mid, cin, 1, dev, g), *_bn(mid, dev, g), _conv_w(mid, mid, 3, dev, g), *_bn(mid, dev, g),
+              _conv_w(cout, mid, 1, dev, g), *_bn(cout, dev, g)]
+    else:
+        ps = [_conv_w(cout, cin, 3, dev, g), *_bn(cout, dev, g), _conv_w(cout, cout, 3, dev, g), *_bn(cout, dev, g)]
     ps += [_conv_w(cout, cin, 1, dev, g), *_bn(cout, dev, g)] if ds else [None] * 5
     for p in ps:
         if isinstance(p, torch.nn.Parameter):
@@ -69,14 +88,14 @@ def test_basic_block_two_segments_equal_two_calls(dev, mode, act, F0, F1, H, cin
                 xs = [x.clone().requires_grad_()]
                 if mode == "fp32h2":
                     ops.amax_compute(xs[0], seg=F0)      # (inside the trunk the producer of the block input records it)
-                ys = [ops.BasicBlockFn.apply(xs[0], stride, True, *ps, F0)]
+                ys = [ops.ResBlockFn.apply(xs[0], stride, True, F0, *ps)]
                 ys[0].backward(gy)
             else:
                 xs = [x[:F0].clone().requires_grad_(), x[F0:].clone().requires_grad_()]
                 if mode == "fp32h2":
                     ops.amax_compute(xs[0])
                     ops.amax_compute(xs[1])
-                ys = [ops.BasicBlockFn.apply(xs[0], stride, True, *ps), ops.BasicBlockFn.apply(xs[1], stride, True, *ps)]
+                ys = [ops.ResBlockFn.apply(xs[0], stride, True, 0, *ps), ops.ResBlockFn.apply(xs[1], stride, True, 0, *ps)]
                 ys[0].backward(gy[:F0])
                 ys[1].backward(gy[F0:])
         finally:
@@ -89,11 +108,13 @@ def test_basic_block_two_segments_equal_two_calls(dev, mode, act, F0, F1, H, cin
         return y, dx, grads, tabs
     y2, dx2, g2, t2 = run(False)
     y1, dx1, g1, t1 = run(True)
-    if mode == "fp32h2":      # the 3x3 launches of both runs took the two-plane form (7 per call without a downsample branch: 2 fwd, 3 dgrad, 2 wgrad)
+    if mode == "fp32h2" and mid:      # three stages: that the two-plane kernels ran, as test_gpu_resnet50.test_bottleneck_isolated asserts
+        assert litemkd_amd.lib().value("lmkd_conv_h2_launches") > h2_before, "two-plane kernels did not run"
+    elif mode == "fp32h2":      # the 3x3 launches of both runs took the two-plane form (7 per call without a downsample branch: 2 fwd, 3 dgrad, 2 wgrad)
         assert litemkd_amd.lib().value("lmkd_conv_h2_launches") - h2_before >= (3 * 5 if stride != 1 else 3 * 6), "two-plane kernels did not run"
     assert torch.equal(y1, y2), _rel(y1.float(), y2.float())
     assert torch.equal(dx1, dx2), _rel(dx1.float(), dx2.float())
-    # deferred tables: the two-call run lists (conv1, conv2, [ds]) of call 0 then of call 1; the merged run lists (seg 0, seg 1) per BatchNorm
+    # deferred tables: the two-call run lists (conv1, conv2, [conv3,] [ds]) of call 0 then of call 1; the merged run lists (seg 0, seg 1) per BatchNorm
     nb = len(t1) // 2
     assert len(t1) == len(t2) == 2 * nb
     for i in range(nb):

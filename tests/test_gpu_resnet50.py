@@ -1,6 +1,6 @@
 """GPU: the ResNet-50 training path (BASELINE configs[4]) under the fp64-anchored criterion of tests/_anchor.py at its REAL map sizes -
 every distinct convolution of the trunk at 224 x 224 (the kernels, tiles and XCD orders of the 200-frame call: tests/_r50_shapes.py) and
-every kind of Bottleneck block (ops.BottleneckFn, hand-scheduled backward) with the HIP path's own ReLU masks imposed on both references.
+every kind of Bottleneck block (ops.ResBlockFn with three stages, hand-scheduled backward) with the HIP path's own ReLU masks imposed on both references.
 Nothing here reads more than a few dozen frames; the measured (HIP, CPU-fp32) pairs go to $LMKD_PARITY_LOG."""
 import pytest
 import torch
@@ -86,7 +86,7 @@ def _bottleneck_ref(case, dt, masks):
 @pytest.mark.parametrize("mode", ["fp32x3", "fp32h2", "fp32"])
 @pytest.mark.parametrize("N,cin,width,H,stride", BOTTLENECK_CASES)
 def test_bottleneck_isolated(dev, N, cin, width, H, stride, mode):
-    """one Bottleneck (ops.BottleneckFn) forward + backward on identical inputs - the twin of test_gpu_ops.test_block_isolated, same
+    """one Bottleneck (ops.ResBlockFn, three stages) forward + backward on identical inputs - the twin of test_gpu_ops.test_block_isolated, same
     structure, same numbers.  The hand-scheduled backward (BatchNorm-backward sums in the 1x1 data gradient's epilogue, in-place dx_out,
     conv1's gradient accumulated onto g, the downsample gradient accumulated at stride 1 and at stride 2, loader-side BatchNorm in
     fp32x3 / fp32 against the materialised activations of fp32h2) is judged per tensor against an fp64 evaluation: error at most 3 x
@@ -179,7 +179,7 @@ def test_persistent_two_plane_1x1_equals_one_workgroup_per_tile(dev):
     """the 1x1 twin of test_gpu_h2.test_persistent_layer1_kernel_equals_one_workgroup_per_tile (3x3 only): r50.l1.reduce256 (256 -> 64, 56 x 56)
     in fp32h2 at 37 frames takes the two-plane 32x32x16 kernel with halo 0 and persistent workgroups; its forward (BatchNorm partial sums,
     recorded maximum) and the 64-column data gradient of the matching expand convolution (plain, accumulating, with the BatchNorm-backward
-    sums in its epilogue - BottleneckFn.backward's da2) are bit-identical to one workgroup per tile (lmkd_conv_set_persistent(0))."""
+    sums in its epilogue - the da of the last stage in ResBlockFn.backward) are bit-identical to one workgroup per tile (lmkd_conv_set_persistent(0))."""
     import litemkd_amd
     from litemkd_amd import ops
     L = litemkd_amd.lib()
