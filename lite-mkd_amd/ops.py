@@ -1526,6 +1526,16 @@ def _resize_plan(n_in, n_out, device):
     return _RESIZE_PLANS[key]
 
 
+def resized_shape(H, W, size):
+    """output (height, width) of Resize(size) on H x W frames (functional.py:44-59): short side -> `size` (int; unchanged if it
+    already matches) or an (h, w) tuple"""
+    if isinstance(size, int):
+        if (W <= H and W == size) or (H <= W and H == size):
+            return H, W
+        return (int(size * H / W), size) if W < H else (size, int(size * W / H))
+    return tuple(size)
+
+
 def resize_frames_u8(frames_u8, size):
     """Resize(size) of the reference's frame transform (video_reader.py:96-101; functional.resize_clip -> PIL BILINEAR) on uint8
     frames [F,H,W,C]: short side -> `size` (int; unchanged if it already matches, functional.py:46-50) or (h, w) tuple.
@@ -1534,13 +1544,8 @@ def resize_frames_u8(frames_u8, size):
     if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4:
         raise RuntimeError("resize_frames_u8 expects uint8 [F,H,W,C] frames")
     F_, H, W, C = frames_u8.shape
-    if isinstance(size, int):
-        if (W <= H and W == size) or (H <= W and H == size):
-            return frames_u8
-        oh, ow = (int(size * H / W), size) if W < H else (size, int(size * W / H))
-    else:
-        oh, ow = size
-    x = frames_u8
+    oh, ow = resized_shape(H, W, size)
+    x = frames_u8                                 # (returned as it is when the size already matches)
     if ow != W:
         b, k, ks = _resize_plan(W, ow, x.device)
         t = torch.empty((F_, H, ow, C), dtype=torch.uint8, device=x.device)
@@ -1554,15 +1559,6 @@ def resize_frames_u8(frames_u8, size):
     return x
 
 
-def _resized_shape(H, W, size):
-    """output (height, width) of Resize(size) on H x W frames (functional.py:44-59)"""
-    if isinstance(size, int):
-        if (W <= H and W == size) or (H <= W and H == size):
-            return H, W
-        return (int(size * H / W), size) if W < H else (size, int(size * W / H))
-    return tuple(size)
-
-
 def frames_resize_crop_nhwc4(frames_u8, resize, crop_y, crop_x, flip, size, frames_per_video=8, out=None):
     """Resize(resize) -> crop (size x size at crop_y / crop_x of the resized frame) -> flip -> ToTensor of uint8 frames [F,H,W,3] that share
     one resolution, in ONE launch (lmkd_frames_resize_crop_nhwc4): bit-identical to resize_frames_u8 + frames_u8_to_nhwc4, without the
@@ -1571,7 +1567,7 @@ def frames_resize_crop_nhwc4(frames_u8, resize, crop_y, crop_x, flip, size, fram
     if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[-1] != 3:
         raise RuntimeError("frames_resize_crop_nhwc4 expects uint8 [F,H,W,3] frames")
     F_, Hs, Ws, _ = frames_u8.shape
-    oh, ow = _resized_shape(Hs, Ws, resize)
+    oh, ow = resized_shape(Hs, Ws, resize)
     nv = F_ // frames_per_video
     if nv * frames_per_video != F_ or crop_y.numel() != nv or crop_x.numel() != nv or flip.numel() != nv:
         raise RuntimeError("one crop/flip entry per video of %d frames expected" % frames_per_video)
@@ -1591,465 +1587,6 @@ def frames_resize_crop_nhwc4(frames_u8, resize, crop_y, crop_x, flip, size, fram
     if _h2_mode():      # ToTensor output lies in [0, 1] (frames_u8_to_nhwc4)
         out._lmkd_amax = _amax_unit_words(out.device)
     return out
-
-
-# ------------------------------------------------------------------------------------------
-# JPEG frames (csrc/jpeg.hip): the decode step of the reference's input chain (video_reader.py:334-343 read_single_image,
-# PIL.Image.open(f).load()) on the GPU, bit-identical to PIL
-# ------------------------------------------------------------------------------------------
-JPEG_SUPPORTED, JPEG_UNSUPPORTED, JPEG_MALFORMED = 0, 1, 2
-JPEG_DEVICE_ERRORS = {1: "bad Huffman code", 2: "coefficient index past 63", 3: "entropy-coded data ends early",
-                      4: "restart marker out of sequence", 5: "data left over at the end of the scan",
-                      6: "entropy-coded data does not fit the decoder's window"}
-_JPEG_STATS = {"images": 0, "gpu": 0, "fallback": 0}
-_JPEG_SCRATCH = {}      # (device index, stream) -> {"in", "coef", "planes"}: grown on demand, reused in stream order
-
-
-def jpeg_stats(reset=False):
-    """images handled by jpeg_decode so far: {"images", "gpu", "fallback"} (fallback: decoded on the host with PIL because the plan
-    marked them unsupported)"""
-    out = dict(_JPEG_STATS)
-    if reset:
-        for k in _JPEG_STATS:
-            _JPEG_STATS[k] = 0
-    return out
-
-
-def _align(n, a=256):
-    return (int(n) + a - 1) // a * a
-
-
-_NOT_UPLOADED = "not uploaded"      # a pinned slot's "event" from PinnedRing.get() until its plan's decode() has queued the H2D copy
-
-
-class PinnedRing:
-    """a ring of pinned host buffers for JpegPlan / PngPlan (pinning a fresh buffer per episode costs milliseconds of hipHostMalloc).
-    A slot's "event" says what may be done with its buffer:
-      None            nothing reads it: reused as it is
-      an event        decode() recorded it after the H2D copy that reads the buffer: reused once it has passed
-      _NOT_UPLOADED   handed to a plan whose decode() has not run yet (a prefetch thread builds plans ahead of the consumer): no event
-                      to wait for, so the buffer stays with that plan and a fresh one takes the slot.  A loader sizes the ring so that
-                      this does not happen in its steady state; when it does, it costs one allocation, never a frame.
-    An ImagePlan draws the buffers of its two formats from two lanes (lane()), each a ring of this size: an episode then takes one slot
-    of a lane whether it holds one format or both, and the ring wraps after the same number of episodes.  pin=False: pageable buffers
-    (a host without a GPU)."""
-
-    def __init__(self, n=6, pin=True):
-        self.slots = [None] * max(2, int(n))
-        self.i = 0
-        self.pin = pin
-        self._lanes = {}
-
-    def lane(self, key):
-        """the ring of the same size that serves `key` alone"""
-        if key not in self._lanes:
-            self._lanes[key] = PinnedRing(len(self.slots), self.pin)
-        return self._lanes[key]
-
-    def get(self, nbytes):
-        k = self.i % len(self.slots)
-        self.i += 1
-        s = self.slots[k]
-        if s is not None and s["event"] is _NOT_UPLOADED:
-            s = None
-        elif s is not None and s["event"] is not None:
-            s["event"].synchronize()
-        if s is None or s["buf"].numel() < nbytes:
-            buf = torch.empty(_align(nbytes * 5 // 4, 1 << 20), dtype=torch.uint8)
-            s = self.slots[k] = {"buf": buf.pin_memory() if self.pin else buf}
-        s["event"] = _NOT_UPLOADED
-        return s
-
-
-def _pil_decode(data, name, convert_rgb=False, label="JPEG"):
-    """the reference's own decoder for the images the plan marks unsupported (progressive, arithmetic, grayscale, interlaced, 16-bit,
-    ...).  convert_rgb: the teacher-side readers' Image.open(path).convert("RGB") (AuxDataset.py:129-136); without it a mode other than
-    RGB raises, as the student-side reader (video_reader.py:334-343) hands the frame transform whatever mode the file has"""
-    import io
-    import numpy as np
-    from PIL import Image
-    try:
-        with Image.open(io.BytesIO(data)) as im:
-            im.load()
-            if im.mode != "RGB":
-                if not convert_rgb:
-                    raise ValueError("%s %s: PIL decodes it as mode %s, the frame transform takes RGB" % (label, name, im.mode))
-                return np.array(im.convert("RGB"))
-            return np.array(im)
-    except (OSError, SyntaxError) as e:      # damage in a file the plan leaves to PIL: named like every other damaged image
-        raise ValueError("%s %s is malformed: PIL refuses it: %s" % (label, name, e)) from e
-
-
-class JpegPlan:
-    """The host half of a batch decode (lmkd_jpeg_plan): the images' bytes, their descriptors and the table pool in ONE host buffer laid
-    out [descriptors | data | pool] (pinned when a GPU is present: one H2D copy of the used prefix), the verdict per image, and the PIL
-    decode of the images the plan marks unsupported (done here, on the thread that builds the plan - a loader's prefetch thread).
-
-    blobs: list of bytes / uint8 tensors, or one packed uint8 tensor with `offsets` (n + 1 byte offsets).  names: optional per-image names
-    for the error messages (a loader passes the frame files).  fallback=False skips the PIL decode (the plan's verdicts alone).
-    convert_rgb: the PIL fallback returns im.convert("RGB") instead of raising on another mode.  index: the images' positions in a
-    larger batch (ImagePlan), used in place of their own in the messages."""
-    _C, _LABEL, _ERRORS, _STATS = "jpeg", "JPEG", JPEG_DEVICE_ERRORS, _JPEG_STATS
-
-    def __init__(self, blobs, offsets=None, names=None, ring=None, pin=None, fallback=True, convert_rgb=False, index=None):
-        import numpy as np
-        if offsets is not None:
-            packed = blobs.reshape(-1) if torch.is_tensor(blobs) else torch.frombuffer(bytearray(blobs), dtype=torch.uint8)
-            offs = [int(o) for o in offsets]
-            blobs = [packed[offs[i]:offs[i + 1]].numpy() for i in range(len(offs) - 1)]
-        else:
-            blobs = [b.cpu().reshape(-1).numpy() if torch.is_tensor(b) else np.frombuffer(b, dtype=np.uint8) for b in blobs]
-        n = len(blobs)
-        if n == 0:
-            raise ValueError("%s_decode: no images" % self._C)
-        self.n, self.names, self.index = n, names, index
-        sizes = [len(b) for b in blobs]
-        dbytes = lib().value("lmkd_%s_desc_bytes" % self._C)
-        self.data_off = _align(n * dbytes)
-        self.pool_off = _align(self.data_off + sum(sizes))
-        pool_cap = lib().value("lmkd_%s_pool_bytes" % self._C, n)
-        need = self.pool_off + pool_cap
-        pin = torch.cuda.is_available() if pin is None else pin
-        if ring is not None and pin:
-            self.slot = ring.get(need)
-        else:
-            buf = torch.empty(need, dtype=torch.uint8)
-            self.slot = {"buf": buf.pin_memory() if pin else buf, "event": None}
-        self.buf = self.slot["buf"]
-        arr = self.buf.numpy()
-        offs = [0]
-        for b in blobs:
-            p = self.data_off + offs[-1]
-            arr[p:p + len(b)] = b
-            offs.append(offs[-1] + len(b))
-        self.offsets = np.asarray(offs, dtype=np.int64)
-        self.info = np.zeros((n, 5), dtype=np.int64)
-        self.totals = np.zeros(5, dtype=np.int64)
-        base = self.buf.data_ptr()
-        lib().call("lmkd_%s_plan" % self._C, ctypes.c_void_p(base + self.data_off), ctypes.c_void_p(self.offsets.ctypes.data), n, ctypes.c_void_p(base),
-                   ctypes.c_void_p(base + self.pool_off), pool_cap, ctypes.c_void_p(self.info.ctypes.data), ctypes.c_void_p(self.totals.ctypes.data))
-        self.nbytes = self.pool_off + int(self.totals[0])          # what the device needs
-        self.fallback = {}
-        if fallback and not (self.info[:, 0] == JPEG_MALFORMED).any():
-            for i in np.nonzero(self.info[:, 0] == JPEG_UNSUPPORTED)[0]:
-                i = int(i)
-                img = _pil_decode(bytes(arr[self.data_off + offs[i]:self.data_off + offs[i + 1]]), self.name(i), convert_rgb, self._LABEL)
-                if img.shape[:2] != self.shape(i):
-                    raise ValueError("%s %s: PIL decodes %s, the header says %s" % (self._LABEL, self.name(i), img.shape[:2], self.shape(i)))
-                t = torch.from_numpy(img)
-                self.fallback[i] = t.pin_memory() if pin else t
-
-    def name(self, i):
-        return "image %d%s" % (i if self.index is None else self.index[i], " (%s)" % self.names[i] if self.names is not None else "")
-
-    def _reason(self, i):
-        return lib().value("lmkd_%s_reason" % self._C, int(self.info[i, 1])).decode()
-
-    def verdicts(self):
-        """[(verdict, reason text)] per image"""
-        return [(int(self.info[i, 0]), self._reason(i)) for i in range(self.n)]
-
-    def shape(self, i):
-        return int(self.info[i, 2]), int(self.info[i, 3])
-
-    def shapes(self):
-        return [self.shape(i) for i in range(self.n)]
-
-    def check(self):
-        """ValueError naming the first image whose header or table the plan found malformed"""
-        for i in range(self.n):
-            if self.info[i, 0] == JPEG_MALFORMED:
-                raise ValueError("%s %s is malformed: %s" % (self._LABEL, self.name(i), self._reason(i)))
-
-    def raise_on_status(self, status):
-        """ValueError naming the first image the GPU decoder stopped (status: the host copy of decode()'s status words)"""
-        for i, s in enumerate(status.tolist() if torch.is_tensor(status) else list(status)):
-            if s:
-                raise ValueError("%s %s is malformed: %s" % (self._LABEL, self.name(i), self._ERRORS.get(int(s), "error %d" % s)))
-
-    def release(self):
-        """this plan will not be decoded: its ring slot may be reused"""
-        if self.slot["event"] is _NOT_UPLOADED:
-            self.slot["event"] = None
-
-    def _scratch(self, key, dev):
-        """the device buffers of this (device, stream): the uploaded plan ("in") and what the launches pass between them"""
-        sc = _JPEG_SCRATCH.get(key)
-        blocks = int(self.totals[1])
-        if sc is None or sc["in"].numel() < self.nbytes or sc["coef"].numel() < blocks * 64:
-            nb = max(self.nbytes, sc["in"].numel() if sc else 0)
-            nk = max(blocks * 64, sc["coef"].numel() if sc else 0, 64)
-            sc = _JPEG_SCRATCH[key] = {"in": torch.empty(_align(nb * 5 // 4, 1 << 20), dtype=torch.uint8, device=dev),
-                                       "coef": torch.empty(_align(nk * 5 // 4), dtype=torch.int16, device=dev),
-                                       "planes": torch.empty(_align(nk * 5 // 4), dtype=torch.uint8, device=dev)}
-        return sc
-
-    def _launch(self, sc, flat, status, stream):
-        base = sc["in"].data_ptr()
-        lib().call("lmkd_jpeg_decode", ctypes.c_void_p(base + self.data_off), ctypes.c_void_p(base), ctypes.c_void_p(base + self.pool_off), self.n,
-                   _p(sc["coef"]), _p(sc["planes"]), _p(flat), _p(status), int(self.totals[3]), int(self.totals[4]), ctypes.c_void_p(stream.cuda_stream))
-
-    def decode(self, out=None, check=True, device=None):
-        """the three decode launches on the current stream (+ the H2D copy, + the copies of the PIL-decoded fallback images) -> (frames,
-        status): frames = uint8 [F, H, W, 3] when every image has the same size (or `out`, any contiguous uint8 tensor of the total size),
-        else a list of [H, W, 3] views; status = int32 device tensor, 0 or the error that stopped the image.  check: read the status words
-        (a synchronisation) and raise ValueError for a malformed image; a streamed loader passes False and reads them later."""
-        self.check()
-        dev = torch.device(device) if device is not None else (out.device if out is not None else torch.device("cuda", torch.cuda.current_device()))
-        stream = torch.cuda.current_stream(dev)
-        total = int(self.totals[2])
-        shapes = self.shapes()
-        uniform = len(set(shapes)) == 1
-        if out is None:
-            out = torch.empty((self.n,) + shapes[0] + (3,) if uniform else (total,), dtype=torch.uint8, device=dev)
-        elif out.dtype != torch.uint8 or not out.is_contiguous() or not out.is_cuda or out.numel() != total:
-            raise RuntimeError("%s_decode: `out` must be a contiguous uint8 device tensor of %d bytes" % (self._C, total))
-        flat = out.view(-1)
-        sc = self._scratch((device_index(dev), stream.cuda_stream), dev)
-        dbuf = sc["in"]
-        dbuf[:self.nbytes].copy_(self.buf[:self.nbytes], non_blocking=True)
-        ev = None                                                   # (a pageable buffer has been read when copy_ returns)
-        if self.buf.is_pinned():
-            ev = torch.cuda.Event()
-            ev.record(stream)
-        self.slot["event"] = ev                                     # the host buffer may be reused once the copy has run
-        status = torch.empty(self.n, dtype=torch.int32, device=dev)
-        self._launch(sc, flat, status, stream)
-        for i, img in self.fallback.items():
-            o = int(self.info[i, 4])
-            flat[o:o + img.numel()].copy_(img.view(-1), non_blocking=True)
-        self._STATS["images"] += self.n
-        self._STATS["fallback"] += len(self.fallback)
-        self._STATS["gpu"] += self.n - len(self.fallback)
-        if check:
-            self.raise_on_status(status.cpu())
-        if out.dim() == 4 or not uniform:
-            frames = out if out.dim() == 4 else [flat[int(self.info[i, 4]):int(self.info[i, 4]) + h * w * 3].view(h, w, 3)
-                                                 for i, (h, w) in enumerate(shapes)]
-        else:
-            frames = flat.view((self.n,) + shapes[0] + (3,))
-        return frames, status
-
-
-def jpeg_decode(blobs, out=None, offsets=None, names=None, check=True):
-    """decode a batch of JPEG images on the GPU (current stream) -> (frames, status): see JpegPlan.decode.  blobs: list of bytes / uint8
-    tensors, one packed uint8 tensor with `offsets`, or a JpegPlan built beforehand (a loader's prefetch thread).  Images the plan marks
-    unsupported are decoded with PIL (counted in jpeg_stats()); a malformed image raises ValueError naming its index."""
-    plan = blobs if isinstance(blobs, JpegPlan) else JpegPlan(blobs, offsets=offsets, names=names)
-    return plan.decode(out=out, check=check)
-
-
-def jpeg_decode_host(blobs, windowed=False, fallback=True):
-    """lmkd_jpeg_decode_host: the device routines run on the CPU (the tests' reference) -> (list of uint8 [H, W, 3] numpy arrays,
-    None for images the plan does not decode on the GPU; the plan; status per image).  windowed: lmkd_jpeg_decode_host_windowed, the
-    entropy launch's own program (window, refill, staging, flush) with the wave's lanes run in turn.  fallback=False builds the plan
-    without the PIL decode of the unsupported images (a batch of damaged files)."""
-    import numpy as np
-    plan = JpegPlan(blobs, pin=False, fallback=fallback)
-    blocks = int(plan.totals[1])
-    coef = torch.zeros(max(64, blocks * 64), dtype=torch.int16).numpy()      # (torch aligns its host buffers to 64 bytes)
-    planes = np.zeros(max(1, blocks * 64), dtype=np.uint8)
-    out = np.zeros(max(1, int(plan.totals[2])), dtype=np.uint8)
-    status = np.zeros(plan.n, dtype=np.int32)
-    base = plan.buf.data_ptr()
-    P = lambda a: ctypes.c_void_p(a.ctypes.data)      # noqa: E731
-    lib().call("lmkd_jpeg_decode_host_windowed" if windowed else "lmkd_jpeg_decode_host", ctypes.c_void_p(base + plan.data_off),
-               ctypes.c_void_p(base), ctypes.c_void_p(base + plan.pool_off), plan.n, P(coef), P(planes), P(out), P(status))
-    imgs = []
-    for i, (h, w) in enumerate(plan.shapes()):
-        o = int(plan.info[i, 4])
-        imgs.append(out[o:o + h * w * 3].reshape(h, w, 3).copy() if plan.info[i, 0] == JPEG_SUPPORTED else None)
-    return imgs, plan, status
-
-
-# ------------------------------------------------------------------------------------------
-# PNG frames (csrc/png.hip, csrc/png_core.h, DESIGN §22): the teacher-side readers' Image.open(path).convert("RGB")
-# (AuxDataset.py:129-136, teacher/code/video_reader.py:190-199) on the GPU, bit-identical to PIL
-# ------------------------------------------------------------------------------------------
-PNG_SUPPORTED, PNG_UNSUPPORTED, PNG_MALFORMED = 0, 1, 2
-PNG_DEVICE_ERRORS = {1: "bad deflate block type", 2: "stored block LEN / NLEN mismatch", 3: "bad code lengths",
-                     4: "invalid length or distance symbol", 5: "distance too far back", 6: "more data than the image holds",
-                     7: "data ends early", 8: "filter type above 4", 9: "Adler-32 mismatch",
-                     10: "compressed data does not fit the decoder's window"}
-_PNG_STATS = {"images": 0, "gpu": 0, "fallback": 0}
-_PNG_SCRATCH = {}      # (device index, stream) -> {"in", "scr"}: grown on demand, reused in stream order
-
-
-def png_stats(reset=False):
-    """images handled by png_decode so far: {"images", "gpu", "fallback"} (fallback: decoded on the host with PIL because the plan marked
-    them unsupported)"""
-    out = dict(_PNG_STATS)
-    if reset:
-        for k in _PNG_STATS:
-            _PNG_STATS[k] = 0
-    return out
-
-
-class PngPlan(JpegPlan):
-    """The host half of a batch PNG decode (lmkd_png_plan): JpegPlan's layout and interface ([descriptors | data | palette pool] in one
-    host buffer, verdicts, the PIL decode of the unsupported images).  The plan moves the IDAT payloads of a supported image together
-    inside this buffer's copy of the file; the caller's bytes are not touched."""
-    _C, _LABEL, _ERRORS, _STATS = "png", "PNG", PNG_DEVICE_ERRORS, _PNG_STATS
-
-    def _scratch(self, key, dev):
-        sc = _PNG_SCRATCH.get(key)
-        nscr = int(self.totals[1])
-        if sc is None or sc["in"].numel() < self.nbytes or sc["scr"].numel() < nscr:
-            nb = max(self.nbytes, sc["in"].numel() if sc else 0)
-            ns = max(nscr, sc["scr"].numel() if sc else 0, 64)
-            sc = _PNG_SCRATCH[key] = {"in": torch.empty(_align(nb * 5 // 4, 1 << 20), dtype=torch.uint8, device=dev),
-                                      "scr": torch.empty(_align(ns * 5 // 4), dtype=torch.uint8, device=dev)}
-        return sc
-
-    def _launch(self, sc, flat, status, stream):
-        """the two decode launches (JpegPlan.decode does the rest)"""
-        trailer = torch.empty(self.n, dtype=torch.int32, device=status.device)
-        base = sc["in"].data_ptr()
-        lib().call("lmkd_png_decode", ctypes.c_void_p(base + self.data_off), ctypes.c_void_p(base), ctypes.c_void_p(base + self.pool_off), self.n,
-                   _p(sc["scr"]), _p(flat), _p(status), _p(trailer), int(self.totals[4]), ctypes.c_void_p(stream.cuda_stream))
-
-
-def png_decode(blobs, out=None, offsets=None, names=None, check=True):
-    """decode a batch of PNG images on the GPU (current stream) -> (frames, status): see PngPlan.decode; the counterpart of jpeg_decode.
-    Images the plan marks unsupported are decoded with PIL (counted in png_stats()); a malformed image raises ValueError naming it."""
-    plan = blobs if isinstance(blobs, PngPlan) else PngPlan(blobs, offsets=offsets, names=names)
-    return plan.decode(out=out, check=check)
-
-
-def png_decode_host(blobs):
-    """lmkd_png_decode_host: the device routines run on the CPU (the tests' reference) -> (list of uint8 [H, W, 3] numpy arrays, None
-    for images the plan does not decode on the GPU; the plan; status per image).  A malformed image keeps its verdict in the plan."""
-    import numpy as np
-    plan = PngPlan(blobs, pin=False, fallback=False)
-    scratch = np.zeros(max(1, int(plan.totals[1])), dtype=np.uint8)
-    out = np.zeros(max(1, int(plan.totals[2])), dtype=np.uint8)
-    status = np.zeros(plan.n, dtype=np.int32)
-    base = plan.buf.data_ptr()
-    P = lambda a: ctypes.c_void_p(a.ctypes.data)      # noqa: E731
-    lib().call("lmkd_png_decode_host", ctypes.c_void_p(base + plan.data_off), ctypes.c_void_p(base), ctypes.c_void_p(base + plan.pool_off),
-               plan.n, P(scratch), P(out), P(status))
-    imgs = []
-    for i, (h, w) in enumerate(plan.shapes()):
-        o = int(plan.info[i, 4])
-        imgs.append(out[o:o + h * w * 3].reshape(h, w, 3).copy() if plan.info[i, 0] == PNG_SUPPORTED else None)
-    return imgs, plan, status
-
-
-def _image_format(blob, label):
-    head = bytes(blob[:4].tolist()) if torch.is_tensor(blob) else bytes(blob[:4])
-    if head[:2] == b"\xff\xd8":
-        return "jpeg"
-    if head == b"\x89PNG":
-        return "png"
-    raise ValueError("%s: neither a JPEG nor a PNG signature (first bytes %s)" % (label, head.hex() or "none"))
-
-
-class ImagePlan:
-    """A batch of frames of either format: the images are sorted by file signature into a JpegPlan and a PngPlan, and the pair answers
-    what trainloop.StreamedEpisodes and the loaders use of a plan: n, shapes(), check(), decode(out=, check=, device=) -> (frames,
-    status), raise_on_status(words), verdicts().  A batch of one format decodes straight into `out`; a mixed one decodes each format
-    into a buffer of its own and places the frames with one device copy per format.  Any other signature raises ValueError naming the
-    file.  convert_rgb: the PIL fallback of both formats returns im.convert("RGB") (the teacher-side readers); without it a frame PIL
-    does not decode as RGB raises (the student-side reader)."""
-
-    def __init__(self, blobs, names=None, ring=None, pin=None, fallback=True, convert_rgb=False):
-        blobs = list(blobs)
-        if not blobs:
-            raise ValueError("image_decode: no images")
-        self.n, self.names = len(blobs), names
-        label = lambda i: "image %d%s" % (i, " (%s)" % names[i] if names is not None else "")      # noqa: E731
-        fmt = [_image_format(b, label(i)) for i, b in enumerate(blobs)]
-        self.plans = []                     # (plan, positions of its images in the batch)
-        for f, cls in (("jpeg", JpegPlan), ("png", PngPlan)):
-            idx = [i for i, g in enumerate(fmt) if g == f]
-            if idx:
-                sub = [names[i] for i in idx] if names is not None else None
-                self.plans.append((cls([blobs[i] for i in idx], names=sub, ring=ring.lane(f) if ring is not None else None, pin=pin, fallback=fallback, convert_rgb=convert_rgb,
-                                       index=idx if len(idx) != self.n else None), idx))
-        self._where = {}
-        for plan, idx in self.plans:
-            for li, i in enumerate(idx):
-                self._where[i] = (plan, li)
-
-    def release(self):
-        """this batch will not be decoded: its ring slots may be reused"""
-        for plan, _ in self.plans:
-            plan.release()
-
-    def fallback_images(self):
-        """{position in the batch: uint8 [H, W, 3] tensor} of the images PIL decoded on the host"""
-        return {idx[li]: img for plan, idx in self.plans for li, img in plan.fallback.items()}
-
-    def shape(self, i):
-        plan, li = self._where[i]
-        return plan.shape(li)
-
-    def shapes(self):
-        return [self.shape(i) for i in range(self.n)]
-
-    def verdicts(self):
-        out = [None] * self.n
-        for plan, idx in self.plans:
-            for i, v in zip(idx, plan.verdicts()):
-                out[i] = v
-        return out
-
-    def check(self):
-        """ValueError naming the first image (in batch order) that its plan found malformed"""
-        for i in range(self.n):
-            plan, li = self._where[i]
-            if plan.info[li, 0] == JPEG_MALFORMED:
-                raise ValueError("%s %s is malformed: %s" % (plan._LABEL, plan.name(li), plan._reason(li)))
-
-    def raise_on_status(self, status):
-        for i, s in enumerate(status.tolist() if torch.is_tensor(status) else list(status)):
-            if s:
-                plan, li = self._where[i]
-                raise ValueError("%s %s is malformed: %s" % (plan._LABEL, plan.name(li), plan._ERRORS.get(int(s), "error %d" % s)))
-
-    def decode(self, out=None, check=True, device=None):
-        self.check()
-        if len(self.plans) == 1:
-            return self.plans[0][0].decode(out=out, check=check, device=device)
-        dev = torch.device(device) if device is not None else (out.device if out is not None else torch.device("cuda", torch.cuda.current_device()))
-        shapes = self.shapes()
-        sizes = [h * w * 3 for h, w in shapes]
-        total = sum(sizes)
-        uniform = len(set(shapes)) == 1
-        if out is None:
-            out = torch.empty((self.n,) + shapes[0] + (3,) if uniform else (total,), dtype=torch.uint8, device=dev)
-        elif out.dtype != torch.uint8 or not out.is_contiguous() or not out.is_cuda or out.numel() != total:
-            raise RuntimeError("image_decode: `out` must be a contiguous uint8 device tensor of %d bytes" % total)
-        flat = out.view(-1)
-        status = torch.zeros(self.n, dtype=torch.int32, device=dev)
-        offs = [0]
-        for s in sizes:
-            offs.append(offs[-1] + s)
-        for plan, idx in self.plans:
-            part = torch.empty(sum(sizes[i] for i in idx), dtype=torch.uint8, device=dev)
-            _, st = plan.decode(out=part, check=False, device=dev)
-            where = torch.tensor(idx, dtype=torch.int64, device=dev)
-            status.index_copy_(0, where, st)
-            if uniform:
-                flat.view(self.n, -1).index_copy_(0, where, part.view(len(idx), -1))
-            else:
-                o = 0
-                for i in idx:
-                    flat[offs[i]:offs[i + 1]].copy_(part[o:o + sizes[i]])
-                    o += sizes[i]
-        if check:
-            self.raise_on_status(status.cpu())
-        if out.dim() == 4 or not uniform:
-            frames = out if out.dim() == 4 else [flat[offs[i]:offs[i + 1]].view(h, w, 3) for i, (h, w) in enumerate(shapes)]
-        else:
-            frames = flat.view((self.n,) + shapes[0] + (3,))
-        return frames, status
-
-
-def image_decode(blobs, out=None, names=None, check=True, convert_rgb=False):
-    """decode a batch of JPEG and / or PNG images on the GPU (current stream) -> (frames, status): see ImagePlan"""
-    plan = blobs if isinstance(blobs, ImagePlan) else ImagePlan(blobs, names=names, convert_rgb=convert_rgb)
-    return plan.decode(out=out, check=check)
 
 
 # parallel.EarlyAllReduce: while set, the trunk's forward registers this tensor hook on the input of its last stage - it fires when the

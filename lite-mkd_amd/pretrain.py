@@ -8,7 +8,7 @@ a label being the class's index in order of first appearance in trainlist03.txt 
 <path>/<class>/<video>/*.jpg, *.jpeg and *.png, sorted by name (any modality: a depth tree of single-channel PNGs is converted to RGB
 as AuxDataset.read_single_image does, Image.open(path).convert("RGB")); the frame choice AuxDataset.get_seq's, which followed through is int(linspace(0, n - 1, seq_len))
 in every mode and for every n (a longer video is first subsampled to seq_len files and then taken whole; a shorter one falls through to
-the same linspace, frames repeating).  Frames are decoded on the GPU (ops.ImagePlan: JPEG and PNG) and transformed by GpuFrameTransform: Resize,
+the same linspace, frames repeating).  Frames are decoded on the GPU (decode.ImagePlan: JPEG and PNG) and transformed by GpuFrameTransform: Resize,
 random flip and crop in --mode train, centre crop otherwise.  An --img_size other than 84 / 224 resizes to round(img_size * 8 / 7).
 
 The loop keeps pretrain.py as it behaves:
@@ -32,7 +32,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import torch
 
-from . import ops
+from . import decode, ops
 from . import trainloop as TL
 
 PRINT_EVERY = 50      # pretrain.py:135
@@ -129,7 +129,7 @@ def frame_transform(img_size, device):
 
 def plan_clips(root, entries, seq_len):
     """the host half of a batch: the chosen frame files of every video, read and planned for the decoder (a malformed header raises,
-    naming its file) -> ops.ImagePlan over len(entries) x seq_len frames, video-major.  convert_rgb: a frame the GPU does not decode
+    naming its file) -> decode.ImagePlan over len(entries) x seq_len frames, video-major.  convert_rgb: a frame the GPU does not decode
     (grayscale JPEG, 16-bit or interlaced PNG, ...) goes through PIL's convert("RGB"), as AuxDataset.read_single_image converts"""
     names = []
     for e in entries:
@@ -139,7 +139,7 @@ def plan_clips(root, entries, seq_len):
     for p in names:
         with open(p, "rb") as f:
             blobs.append(f.read())
-    plan = ops.ImagePlan(blobs, names=names, convert_rgb=True)
+    plan = decode.ImagePlan(blobs, names=names, convert_rgb=True)
     plan.check()
     return plan
 
@@ -148,18 +148,13 @@ def load_clips(plan, n_videos, seq_len, tf, train, check=True):
     """decode a planned batch (n_videos x seq_len JPEG / PNG frames, video-major) and transform it -> (NHWC4 [n_videos * seq_len, S, S, 4], the
     decoder's status words); check=False leaves reading them (a synchronisation) to the caller: plan.raise_on_status(status.cpu())"""
     frames, status = plan.decode(check=check)
-    L = seq_len
-    if torch.is_tensor(frames):
-        videos = [frames[i * L:(i + 1) * L] for i in range(n_videos)]
-    else:
-        videos = [torch.stack(frames[i * L:(i + 1) * L]) for i in range(n_videos)]
-    return tf(videos, train=train), status
+    return tf(decode.split_videos(frames, seq_len), train=train), status
 
 
 class ClipBatches:
     """DataLoader(AuxDataset, batch_size, shuffle=True) with getitem get_video_with_label: every pass is a fresh permutation of the list,
     the last batch may be smaller.  A batch: (NHWC4 frames [B * T, S, S, 4] on the device, int64 labels [B] on the host, the entries).
-    The files of the next batches are read and planned (ops.ImagePlan) on `workers` host threads while the current one runs."""
+    The files of the next batches are read and planned (decode.ImagePlan) on `workers` host threads while the current one runs."""
 
     def __init__(self, args, device, shuffle=True):
         self.args, self.device, self.shuffle = args, device, shuffle

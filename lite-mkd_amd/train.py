@@ -244,7 +244,7 @@ class ClipDirectoryEpisodes:
             yield self.episode()
 
 
-FRAME_EXTENSIONS = (".jpg", ".jpeg", ".png")      # decoded on the GPU (ops.ImagePlan sorts a batch by file signature)
+FRAME_EXTENSIONS = (".jpg", ".jpeg", ".png")      # decoded on the GPU (decode.ImagePlan sorts a batch by file signature)
 
 
 def jpeg_frame_index(rgb_path):
@@ -301,13 +301,13 @@ class JpegFrameEpisodes(ClipDirectoryEpisodes):
 
     The draws are ClipDirectoryEpisodes' own (_draw: classes, videos, frames, shuffles, then flip / crop), so a seeded run picks the same
     episode from a JPEG tree as from the .npy tree of the same decoded frames; only the seq_len selected files of a video are read.  The
-    frames are decoded on the GPU (ops.ImagePlan: csrc/jpeg.hip, csrc/png.hip; bit-identical to PIL; a frame that PIL does not decode as
+    frames are decoded on the GPU (decode.ImagePlan: csrc/jpeg.hip, csrc/png.hip; bit-identical to PIL; a frame that PIL does not decode as
     RGB raises, since the reference's student reader, video_reader.py:334-343, does not convert): episode() decodes and transforms on the current
     stream; host_episode() hands trainloop.StreamedEpisodes the compressed bytes of the episode, packed into one pinned buffer with
     their decode plan, in place of "frames"."""
 
     def __init__(self, config, rgb_path, traintestlist=None, teacher_path=None, split=None, device="cuda", length=10 ** 9, train=True):
-        from . import ops
+        from . import decode
         from .video_transform import GpuFrameTransform
         self.c, self.root, self.froot, self.device, self.length, self.train = config, rgb_path, teacher_path, device, length, train
         self.dataset = self
@@ -341,7 +341,7 @@ class JpegFrameEpisodes(ClipDirectoryEpisodes):
             raise ValueError("%s holds %d classes in the %s split, the episodes need %d"
                              % (rgb_path, len(self.splits[bool(train)]), "train" if train else "test", config.way))
         self.tf = GpuFrameTransform(config.img_size, device)
-        self._ring = ops.PinnedRing(6)
+        self._ring = decode.PinnedRing(6)
 
     @property
     def classes(self):
@@ -366,11 +366,11 @@ class JpegFrameEpisodes(ClipDirectoryEpisodes):
         return torch.from_numpy(np.load(self._feat[(cname, vid)])).float()
 
     def _plan(self, train):
-        from . import ops
+        from . import decode
         sup, tgt = self._draw(train)
         names = [v[2][i] for v in sup + tgt for i in v[3]]
-        plan = ops.ImagePlan([self._read(p) for p in names], names=names, ring=self._ring if torch.cuda.is_available() else None,
-                             convert_rgb=False)
+        plan = decode.ImagePlan([self._read(p) for p in names], names=names, ring=self._ring if torch.cuda.is_available() else None,
+                                convert_rgb=False)
         plan.check()                        # a malformed header names its file here
         return sup, tgt, plan
 
@@ -383,19 +383,16 @@ class JpegFrameEpisodes(ClipDirectoryEpisodes):
                              % sorted(set(shapes)))
         L = self.c.seq_len
         params = [self.tf.draw(shapes[i * L][0], shapes[i * L][1], train) for i in range(len(sup) + len(tgt))]
-        d = {"jpeg": plan, "params": params, "features": torch.stack([self._feature(v[0], v[1]) for v in sup + tgt]), "ns": len(sup)}
+        d = {"plan": plan, "params": params, "features": torch.stack([self._feature(v[0], v[1]) for v in sup + tgt]), "ns": len(sup)}
         d.update(self._labels(sup, tgt, self.c.way))
         return d
 
     def episode(self):
         train = self.train
         sup, tgt, plan = self._plan(train)
+        from . import decode
         frames, _ = plan.decode(check=True)
-        L = self.c.seq_len
-        if torch.is_tensor(frames):
-            videos = [frames[i * L:(i + 1) * L] for i in range(len(sup) + len(tgt))]
-        else:
-            videos = [torch.stack(frames[i * L:(i + 1) * L]) for i in range(len(sup) + len(tgt))]
+        videos = decode.split_videos(frames, self.c.seq_len)
         return self._task(videos[:len(sup)], videos[len(sup):], sup, tgt, train)
 
 

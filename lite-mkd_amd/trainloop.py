@@ -439,9 +439,9 @@ class StreamedEpisodes:
     episodes whose backward passes PipelinedEpisodes has not queued yet (i - PIPELINE_DEPTH ... i - 1), of episode i (staged, about to be
     handed out) and of episode i + 1 itself: hence sets >= PIPELINE_DEPTH + 2, and the constructor raises `sets` to that.
 
-    A source may hand over COMPRESSED frames instead (train.JpegFrameEpisodes): "jpeg" = an ops.JpegPlan (the JPEG bytes, descriptors and
-    table pool in one pinned buffer) in place of "frames"; the copy stream then uploads it and runs the three decode launches into the
-    set's uint8 buffer before the frame transform.  The decoder's status words are read when a later episode is staged, without a
+    A source may hand over COMPRESSED frames instead (train.JpegFrameEpisodes): "plan" = a decode.ImagePlan (the bytes of the episode's JPEG
+    and / or PNG frames, their descriptors and table pool in one pinned buffer per format) in place of "frames"; the copy stream then
+    uploads it and runs its decode launches into the set's uint8 buffer before the frame transform.  The decoder's status words are read when a later episode is staged, without a
     synchronisation: a malformed frame raises ValueError (naming its file) an episode or two late.  One prefetch generation per mode:
     when dataset.train changes (test() in mid-training) the producer is stopped, queued and held episodes are dropped and a producer
     for the new mode starts."""
@@ -468,7 +468,7 @@ class StreamedEpisodes:
         self._gen = 0                       # prefetch generation: one per mode (train / test) the loader serves in turn
         self._mode = None
         self._ahead = None                  # the current generation's episode staged ahead of the loop's request, not handed out yet
-        self._jpeg_pending = []             # (set index, event, pinned status words, plan) of staged JPEG episodes, not yet checked
+        self._decode_pending = []             # (set index, event, pinned status words, plan) of staged compressed episodes, not yet checked
         self.length = getattr(source, "length", 10 ** 9)
         self.staged = 0
 
@@ -493,7 +493,7 @@ class StreamedEpisodes:
     def _pinned(self, h, n):
         """the episode's frames and features in pinned memory.  A source that decodes into pinned memory of its own keeps it alive until the
         episode has been staged; anything else is copied into slot n of the ring.  (Compressed frames come packed in pinned memory.)"""
-        dtypes = {"features": torch.float32} if "jpeg" in h else {"frames": torch.uint8, "features": torch.float32}
+        dtypes = {"features": torch.float32} if "plan" in h else {"frames": torch.uint8, "features": torch.float32}
         if all(h[k].is_pinned() for k in dtypes) and h["features"].dtype is torch.float32:
             return h
         slot = self._pins[n % len(self._pins)]
@@ -511,8 +511,8 @@ class StreamedEpisodes:
 
     def _set(self, k, h):
         s = self.sets[k]
-        if "jpeg" in h:
-            shapes = h["jpeg"].shapes()
+        if "plan" in h:
+            shapes = h["plan"].shapes()
             F_, H, W = len(shapes), shapes[0][0], shapes[0][1]
         else:
             F_, H, W, _ = h["frames"].shape
@@ -537,21 +537,21 @@ class StreamedEpisodes:
         s = self._set(k, h)
         s["busy"] = True
         L = h["features"].shape[1]
-        self._jpeg_check(k)
+        self._decode_check(k)
         with torch.cuda.stream(self.copy):
             for ev in s["free"]:
                 self.copy.wait_event(ev)                   # every stream that read this set last time has passed
             s["free"] = []
-            if "jpeg" in h:
-                # upload of the packed bytes + descriptors + table pool, the three decode launches (csrc/jpeg.hip) into the set's uint8
+            if "plan" in h:
+                # upload of the packed bytes + descriptors + table pool, the decode launches (csrc/jpeg.hip, csrc/png.hip) into the set's uint8
                 # frames; the status words go to pinned memory and are read when a later episode is staged (no synchronisation here)
-                plan = h["jpeg"]
+                plan = h["plan"]
                 _, status = plan.decode(out=s["u8"], check=False, device=self.device)
                 words = torch.empty(status.shape, dtype=torch.int32).pin_memory()
                 words.copy_(status, non_blocking=True)
                 ev = torch.cuda.Event()
                 ev.record(self.copy)
-                self._jpeg_pending.append((k, ev, words, plan))
+                self._decode_pending.append((k, ev, words, plan))
             else:
                 s["u8"].copy_(h["frames"], non_blocking=True)
             s["feat"].copy_(h["features"], non_blocking=True)
@@ -591,11 +591,11 @@ class StreamedEpisodes:
                 t.record_stream(st)
         s["busy"] = False
 
-    def _jpeg_check(self, k=None):
-        """read the status words of staged JPEG episodes whose copy has finished (and, for set k, which is about to be overwritten, wait for
+    def _decode_check(self, k=None):
+        """read the status words of staged compressed episodes whose copy has finished (and, for set k, which is about to be overwritten, wait for
         it: it was staged several episodes ago) -> ValueError naming the frame file the GPU decoder stopped on"""
         keep = []
-        for item in self._jpeg_pending:
+        for item in self._decode_pending:
             kk, ev, words, plan = item
             if kk == k or k is None:
                 ev.synchronize()
@@ -603,7 +603,7 @@ class StreamedEpisodes:
                 keep.append(item)
                 continue
             plan.raise_on_status(words)
-        self._jpeg_pending = keep
+        self._decode_pending = keep
 
     def _stop_thread(self):
         if self._thread is not None:
@@ -666,7 +666,7 @@ class StreamedEpisodes:
 
     def close(self):
         self._stop_thread()
-        self._jpeg_check()
+        self._decode_check()
 
 
 def init_model(config):

@@ -25,10 +25,7 @@ class GpuFrameTransform:
         self.img_size, self.resize, self.device = img_size, resize, device
 
     def resized_hw(self, h, w):
-        s = self.resize                                                # functional.py:45-52,66-73
-        if (w <= h and w == s) or (h <= w and h == s):
-            return h, w
-        return (int(s * h / w), s) if w < h else (s, int(s * w / h))
+        return ops.resized_shape(h, w, self.resize)
 
     def draw(self, h, w, train):
         """-> (flip, x1, y1) for one video whose decoded frames are h x w, consuming `random` like the reference"""
@@ -81,7 +78,7 @@ class GpuFrameTransform:
         [F, H, W, 3] (one H2D copy of the whole episode): resize + crop / flip / ToTensor in one launch + the crop parameters.
         params: [(flip, x1, y1)] per video (draw()).  out: optional preallocated [F, S, S, 4] fp32 tensor (static input buffers)."""
         S = self.img_size
-        _, ow = ops._resized_shape(frames_u8.shape[1], frames_u8.shape[2], self.resize)
+        _, ow = self.resized_hw(frames_u8.shape[1], frames_u8.shape[2])
         i32 = lambda vals: torch.tensor(vals, dtype=torch.int32).pin_memory().to(self.device, non_blocking=True)      # noqa: E731
         cx = [(ow - S - p[1]) if p[0] else p[1] for p in params]
         # one launch (round 5; before: two resize passes + the crop kernel, 1.08 ms of a streamed episode's copy-stream work)

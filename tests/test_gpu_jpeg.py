@@ -1,4 +1,4 @@
-"""GPU: JPEG frames decoded on the MI355X (csrc/jpeg.hip through ops.jpeg_decode) bit-identical to PIL, malformed scans isolated to their
+"""GPU: JPEG frames decoded on the MI355X (csrc/jpeg.hip through decode.jpeg_decode) bit-identical to PIL, malformed scans isolated to their
 image, train.JpegFrameEpisodes giving the same episodes as ClipDirectoryEpisodes over the same decoded frames (directly and through
 trainloop.StreamedEpisodes), the --rgb_path command lines, and no train / test mixing when test() runs in mid-training."""
 import io
@@ -35,23 +35,23 @@ def _fixtures():
 
 
 def test_fixtures_one_mixed_batch_bit_exact(dev):
-    from litemkd_amd import ops
+    from litemkd_amd import decode
     fx = _fixtures()
-    before = ops.jpeg_stats()
-    frames, status = ops.jpeg_decode([f[1] for f in fx])
+    before = decode.jpeg_stats()
+    frames, status = decode.jpeg_decode([f[1] for f in fx])
     assert isinstance(frames, list) and len(frames) == len(fx)          # mixed sizes: one view per image
     assert not status.cpu().any()
     first = [f.cpu() for f in frames]
     for (name, _, ref), got in zip(fx, first):
         assert np.array_equal(got.numpy(), ref), (name, int((got.numpy() != ref).sum()))
-    after = ops.jpeg_stats()
+    after = decode.jpeg_stats()
     assert after["fallback"] - before["fallback"] == 1 and after["gpu"] - before["gpu"] == len(fx) - 1      # the progressive fixture
-    frames2, _ = ops.jpeg_decode([f[1] for f in fx])
+    frames2, _ = decode.jpeg_decode([f[1] for f in fx])
     assert all(torch.equal(a, b.cpu()) for a, b in zip(first, frames2))
     # one size: one [F, H, W, 3] tensor, into a caller's buffer too
     same = [f for f in fx if f[0].startswith("53x37_ss2")]
     out = torch.empty((len(same), 37, 53, 3), dtype=torch.uint8, device=dev)
-    got, _ = ops.jpeg_decode([f[1] for f in same], out=out)
+    got, _ = decode.jpeg_decode([f[1] for f in same], out=out)
     assert got is out and all(np.array_equal(out[i].cpu().numpy(), f[2]) for i, f in enumerate(same))
 
 
@@ -60,13 +60,13 @@ def test_altered_scan_is_malformed_and_isolated(dev):
     tools/jpeg_host_check.cpp) between good images, in one batch: an EOI planted half way, one case per status word 1..5, and four
     321x239 cases damaged beyond the first 8 KiB window (two the host twin flags, two it does not).  The GPU gives the host twin's
     status list, the good images bit for bit, the host twin's pixels for the unflagged damaged ones, and the same bits twice."""
-    from litemkd_amd import ops
+    from litemkd_amd import decode
     good = [U.fixture(n) for n in ("53x37_ss1_q95", "53x37_ss0_restart_marker_rows", "320x240_ss2_q75")]
     cases = U.full_matrix() + [U.renumbered_rst()]
-    _, hplan, hs = ops.jpeg_decode_host([c[1] for c in cases], fallback=False)
+    _, hplan, hs = decode.jpeg_decode_host([c[1] for c in cases], fallback=False)
     pick, deep = {}, {True: [], False: []}
     for (label, data), (v, _), s in zip(cases, hplan.verdicts(), hs.tolist()):
-        if v != ops.JPEG_SUPPORTED:
+        if v != decode.SUPPORTED:
             continue
         if s not in pick and (s == 3 if "cut@" in label else s == 4 if "rst@" in label else s in (1, 2, 5)):
             pick[s] = (label, data)
@@ -77,9 +77,9 @@ def test_altered_scan_is_malformed_and_isolated(dev):
              + [c[1] for c in deep[True] + deep[False]] + [good[2][1]])
     names = ["g0.jpg", "eoi.jpg", "s1.jpg", "s2.jpg", "s3.jpg", "s4.jpg", "s5.jpg", "g1.jpg", "deep_f0.jpg", "deep_f1.jpg", "deep_u0.jpg",
              "deep_u1.jpg", "g2.jpg"]
-    himgs, _, hstatus = ops.jpeg_decode_host(blobs, fallback=False)
+    himgs, _, hstatus = decode.jpeg_decode_host(blobs, fallback=False)
     assert hstatus.tolist()[2:7] == [1, 2, 3, 4, 5] and hstatus.tolist()[10:] == [0, 0, 0] and all(hstatus.tolist()[8:10])
-    frames, status = ops.jpeg_decode(blobs, check=False)
+    frames, status = decode.jpeg_decode(blobs, check=False)
     st = status.cpu().tolist()
     assert st == hstatus.tolist(), (st, hstatus.tolist())
     assert st[0] == 0 and st[1] != 0 and st[7] == 0 and st[12] == 0
@@ -89,18 +89,18 @@ def test_altered_scan_is_malformed_and_isolated(dev):
     for k in (10, 11):                                   # damaged, not flagged: whatever libjpeg makes of them, the host twin's pixels
         assert np.array_equal(first[k], himgs[k]), names[k]
         assert not np.array_equal(first[k], U.fixture("321x239_ss1_q90_rows")[2]), names[k]
-    frames2, status2 = ops.jpeg_decode(blobs, check=False)
+    frames2, status2 = decode.jpeg_decode(blobs, check=False)
     # the same bits twice, the stopped images included: the blocks a stopped image never wrote keep what the scratch held, and the two
     # decodes share the scratch of this (device, stream) with nothing in between
     assert status2.cpu().tolist() == st
     assert all(np.array_equal(a, b.cpu().numpy()) for a, b in zip(first, frames2)), [n for n, a, b in zip(names, first, frames2)
                                                                                     if not np.array_equal(a, b.cpu().numpy())]
     with pytest.raises(ValueError, match=r"JPEG image 1 \(eoi\.jpg\) is malformed"):
-        ops.jpeg_decode(blobs, names=names)
+        decode.jpeg_decode(blobs, names=names)
     with pytest.raises(ValueError, match="image 1"):
-        ops.jpeg_decode(blobs)
+        decode.jpeg_decode(blobs)
     with pytest.raises(ValueError, match="image 0 .*malformed"):
-        ops.jpeg_decode([good[0][1][:40]])
+        decode.jpeg_decode([good[0][1][:40]])
 
 
 def _frame(value, g, h=100, w=132):

@@ -1329,7 +1329,7 @@ def test_fused_frame_transform_equals_two_pass_and_pillow(dev, shape, resize, S)
     H, W = shape
     L, nv = 4, 5
     frames = rng.integers(0, 256, (L * nv, H, W, 3), dtype=np.uint8)
-    oh, ow = ops._resized_shape(H, W, resize)
+    oh, ow = ops.resized_shape(H, W, resize)
     cy = torch.tensor([0, oh - S, (oh - S) // 2, 1 % (oh - S + 1), oh - S], dtype=torch.int32)
     cx = torch.tensor([0, ow - S, (ow - S) // 3, ow - S, 0], dtype=torch.int32)
     fl = torch.tensor([0, 1, 1, 0, 1], dtype=torch.int32)

@@ -1,5 +1,5 @@
-"""GPU: PNG frames decoded on the MI355X (csrc/png.hip through ops.png_decode) bit-identical to PIL's convert("RGB"); streams the host
-twin has already shown to stop cleanly stop their own image only; ops.ImagePlan over PNG and JPEG frames into one preallocated tensor;
+"""GPU: PNG frames decoded on the MI355X (csrc/png.hip through decode.png_decode) bit-identical to PIL's convert("RGB"); streams the host
+twin has already shown to stop cleanly stop their own image only; decode.ImagePlan over PNG and JPEG frames into one preallocated tensor;
 a depth-like tree of grayscale PNGs through extract --stage modality, and a PNG tree through train.JpegFrameEpisodes and
 trainloop.StreamedEpisodes, against the same pipeline fed with PIL's decodes."""
 import io
@@ -27,41 +27,41 @@ def dev():
 
 
 def test_fixtures_one_mixed_batch_bit_exact(dev):
-    from litemkd_amd import ops
+    from litemkd_amd import decode
     fx = [f for f in U.fixtures() if f[3]]
     assert len(fx) >= 56
-    before = ops.png_stats()
-    frames, status = ops.png_decode([f[1] for f in fx])
+    before = decode.png_stats()
+    frames, status = decode.png_decode([f[1] for f in fx])
     assert isinstance(frames, list) and len(frames) == len(fx)               # mixed sizes: one view per image
     st = status.cpu().tolist()
     assert not any(st), [(f[0], s) for f, s in zip(fx, st) if s]
     first = [f.cpu() for f in frames]
     for (name, _, ref, _), got in zip(fx, first):
         assert tuple(got.shape) == ref.shape and np.array_equal(got.numpy(), ref), (name, int((got.numpy() != ref).sum()))
-    after = ops.png_stats()
+    after = decode.png_stats()
     assert after["fallback"] - before["fallback"] == 0 and after["gpu"] - before["gpu"] == len(fx) == after["images"] - before["images"]
-    frames2, _ = ops.png_decode([f[1] for f in fx])                          # the scratch buffers are reused
+    frames2, _ = decode.png_decode([f[1] for f in fx])                          # the scratch buffers are reused
     assert all(torch.equal(a, b.cpu()) for a, b in zip(first, frames2))
     # the fallback set goes through PIL (convert_rgb: these are not RGB files) and is counted
     fb = [f for f in U.fixtures() if not f[3]]
-    after = ops.png_stats()
-    plan = ops.PngPlan([f[1] for f in fb], convert_rgb=True)
+    after = decode.png_stats()
+    plan = decode.PngPlan([f[1] for f in fb], convert_rgb=True)
     frames, status = plan.decode()
     assert not status.cpu().any()
     for (name, _, ref, _), got in zip(fb, frames):
         assert np.array_equal(got.cpu().numpy(), ref), name
-    last = ops.png_stats()
+    last = decode.png_stats()
     assert last["fallback"] - after["fallback"] == len(fb) == 4 and last["gpu"] == after["gpu"]
     with pytest.raises(ValueError, match="the frame transform takes RGB"):
-        ops.png_decode([fb[1][1]])
+        decode.png_decode([fb[1][1]])
 
 
 def test_altered_streams_stop_their_own_image(dev):
     """three streams of the host corruption matrix that the host twin stopped with 'distance too far back', 'data ends early' and
     'Adler-32 mismatch', between good images"""
-    from litemkd_amd import ops
+    from litemkd_amd import decode
     cases = U.corruption_matrix("53x37_t2_mix", flips=200, seed=0)
-    _, _, hs = ops.png_decode_host([c[1] for c in cases])
+    _, _, hs = decode.png_decode_host([c[1] for c in cases])
     pick = {}
     for (label, data), s in zip(cases, hs.tolist()):
         if s not in pick and (s == 7 if "cut@" in label else s in (5, 9)):
@@ -70,14 +70,14 @@ def test_altered_streams_stop_their_own_image(dev):
     good = [U.fixture(n) for n in ("53x37_t6_mix", "53x37_t3_trns", "321x239_t2_mix")]
     blobs = [good[0][1], pick[5][1], good[1][1], pick[7][1], pick[9][1], good[2][1]]
     names = ["g0.png", "far.png", "g1.png", "cut.png", "adler.png", "g2.png"]
-    frames, status = ops.png_decode(blobs, check=False)
+    frames, status = decode.png_decode(blobs, check=False)
     assert status.cpu().tolist() == [0, 5, 0, 7, 9, 0]
     for k, g in zip((0, 2, 5), good):
         assert np.array_equal(frames[k].cpu().numpy(), g[2]), g[0]
     with pytest.raises(ValueError, match=r"PNG image 1 \(far\.png\) is malformed: distance too far back"):
-        ops.png_decode(blobs, names=names)
+        decode.png_decode(blobs, names=names)
     with pytest.raises(ValueError, match=r"image 0 .*malformed: truncated chunk"):
-        ops.png_decode([good[0][1][:90]])
+        decode.png_decode([good[0][1][:90]])
 
 
 def _jpeg_fixtures():
@@ -87,17 +87,17 @@ def _jpeg_fixtures():
 
 
 def test_image_plan_into_one_tensor(dev):
-    from litemkd_amd import ops
+    from litemkd_amd import decode
     png = [f for f in U.fixtures() if f[0].startswith("53x37") and f[3]]
     jpg = [f for f in _jpeg_fixtures() if f[0].startswith("53x37") and "progressive" not in f[0]]
     assert len(png) >= 30 and len(jpg) >= 12
     # all PNG: straight into the caller's tensor
     out = torch.empty((len(png), 37, 53, 3), dtype=torch.uint8, device=dev)
-    plan = ops.ImagePlan([f[1] for f in png], names=[f[0] for f in png])
+    plan = decode.ImagePlan([f[1] for f in png], names=[f[0] for f in png])
     assert plan.shapes() == [(37, 53)] * len(png)
     got, status = plan.decode(out=out, check=False)
     assert got is out and not status.cpu().any()
-    alone, _ = ops.png_decode([f[1] for f in png])
+    alone, _ = decode.png_decode([f[1] for f in png])
     assert torch.equal(out, alone) and all(np.array_equal(out[i].cpu().numpy(), f[2]) for i, f in enumerate(png))
     # JPEG and PNG interleaved
     mixed, ref = [], []
@@ -106,43 +106,43 @@ def test_image_plan_into_one_tensor(dev):
         mixed.append(f[1])
         ref.append(f[2])
     out = torch.full((len(mixed), 37, 53, 3), 7, dtype=torch.uint8, device=dev)
-    plan = ops.ImagePlan(mixed)
+    plan = decode.ImagePlan(mixed)
     got, status = plan.decode(out=out, check=True)
     assert got is out and status.shape == (len(mixed),) and not status.cpu().any()
-    ja, _ = ops.jpeg_decode(mixed[0::2])
-    pa, _ = ops.png_decode(mixed[1::2])
+    ja, _ = decode.jpeg_decode(mixed[0::2])
+    pa, _ = decode.png_decode(mixed[1::2])
     assert torch.equal(out[0::2], ja) and torch.equal(out[1::2], pa)
     assert all(np.array_equal(out[i].cpu().numpy(), r) for i, r in enumerate(ref))
     # mixed sizes and formats without `out`: a list of views in batch order
     big = U.fixture("321x239_t0_mix")
-    frames, _ = ops.image_decode([jpg[0][1], big[1], png[0][1]])
+    frames, _ = decode.image_decode([jpg[0][1], big[1], png[0][1]])
     assert [tuple(f.shape) for f in frames] == [(37, 53, 3), (239, 321, 3), (37, 53, 3)]
     assert np.array_equal(frames[1].cpu().numpy(), big[2]) and np.array_equal(frames[0].cpu().numpy(), jpg[0][2])
     # a bad stream inside a mixed batch is reported under its position in the batch
     bad = U.with_stream(png[0][1], U.stream_of(png[0][1])[:200])
     with pytest.raises(ValueError, match=r"PNG image 1 \(b\) is malformed: data ends early"):
-        ops.image_decode([jpg[0][1], bad, png[1][1]], names=["a", "b", "c"])
+        decode.image_decode([jpg[0][1], bad, png[1][1]], names=["a", "b", "c"])
 
 
 def test_mixed_episodes_staged_past_the_ring(dev):
     """a loader's prefetch thread stages episodes ahead of the consumer in a PinnedRing: more mixed episodes than the ring has slots,
     none decoded before all are built, each then decodes to its own frames; afterwards the slots are reused in place"""
-    from litemkd_amd import ops
+    from litemkd_amd import decode
     png = [f for f in U.fixtures() if f[0].startswith("53x37") and f[3]]
     jpg = [f for f in _jpeg_fixtures() if f[0].startswith("53x37") and "progressive" not in f[0]]
-    ring = ops.PinnedRing(2)
+    ring = decode.PinnedRing(2)
 
     def files(k):
         return [jpg[k % len(jpg)], png[k % len(png)], png[(k + 7) % len(png)], jpg[(k + 3) % len(jpg)]]
 
-    staged = [ops.ImagePlan([f[1] for f in files(k)], ring=ring) for k in range(5)]
+    staged = [decode.ImagePlan([f[1] for f in files(k)], ring=ring) for k in range(5)]
     assert all(p.buf.is_pinned() for plan in staged for p, _ in plan.plans)
     for k, plan in enumerate(staged):
         out = torch.empty((4, 37, 53, 3), dtype=torch.uint8, device=dev)
         _, status = plan.decode(out=out, check=True)
         assert all(np.array_equal(out[i].cpu().numpy(), f[2]) for i, f in enumerate(files(k))), k
     held = {p.buf.data_ptr() for plan in staged[3:] for p, _ in plan.plans}              # the ring's four buffers now
-    again = [ops.ImagePlan([f[1] for f in files(k)], ring=ring) for k in (5, 6)]         # waits for the uploads, allocates nothing
+    again = [decode.ImagePlan([f[1] for f in files(k)], ring=ring) for k in (5, 6)]         # waits for the uploads, allocates nothing
     assert {p.buf.data_ptr() for plan in again for p, _ in plan.plans} == held
     for k, plan in zip((5, 6), again):
         frames, _ = plan.decode()
@@ -159,7 +159,7 @@ def test_depth_tree_through_extract(dev, tmp_path):
     extract --stage modality, against the same model fed with PIL's convert("RGB") of the same files"""
     from PIL import Image
     from litemkd_amd import extract as E
-    from litemkd_amd import ops
+    from litemkd_amd import decode
     from litemkd_amd import pretrain as PT
     depth, lists = tmp_path / "depth", tmp_path / "lists"
     lists.mkdir()
@@ -181,9 +181,9 @@ def test_depth_tree_through_extract(dev, tmp_path):
     args = E.args_check(parser, parser.parse_args(flags + ["--out", str(tmp_path / "ref")]))
     torch.manual_seed(7)
     torch.save({"model_state_dict": {k: v.detach().cpu() for k, v in PT.build_model(args, dev).state_dict().items()}}, ck)
-    before = ops.png_stats()
+    before = decode.png_stats()
     rec = E.main(flags + ["--out", str(tmp_path / "feats")])
-    after = ops.png_stats()
+    after = decode.png_stats()
     assert (rec["written"], rec["skipped"], rec["model_calls"]) == (4, 0, 1)
     assert after["images"] - before["images"] == 32 and after["fallback"] - before["fallback"] == 1
     model = E.build_modality_model(args, dev)

@@ -224,8 +224,8 @@ def test_resized_shape_and_identity_plan():
     from oracle import ref_cpu as O
     for (h, w) in [(240, 320), (320, 240), (256, 300), (256, 256), (288, 352), (100, 256), (17, 9)]:
         for size in (256, 128, 17):
-            assert ops._resized_shape(h, w, size) == O.resize_short_side(h, w, size), (h, w, size)
-    assert ops._resized_shape(240, 320, (80, 72)) == (80, 72)
+            assert ops.resized_shape(h, w, size) == O.resize_short_side(h, w, size), (h, w, size)
+    assert ops.resized_shape(240, 320, (80, 72)) == (80, 72)
     L = litemkd_amd.lib()
     for n in (5, 224, 341):
         ks = L.value("lmkd_resize_plan", n, n, None, None)

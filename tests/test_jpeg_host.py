@@ -23,14 +23,14 @@ def _baseline():
 
 
 def _verdict(data):
-    from litemkd_amd import ops
-    return ops.JpegPlan([data], pin=False, fallback=False).verdicts()[0]
+    from litemkd_amd import decode
+    return decode.JpegPlan([data], pin=False, fallback=False).verdicts()[0]
 
 
 def test_plan_verdicts():
-    from litemkd_amd import ops
+    from litemkd_amd import decode
     base = _baseline()
-    assert _verdict(base) == (ops.JPEG_SUPPORTED, "supported")
+    assert _verdict(base) == (decode.SUPPORTED, "supported")
     segs = _segments(base)
     sof = [i for i, s in enumerate(segs) if s[0] == 0xC0][0]
     dqt = [i for i, s in enumerate(segs) if s[0] == 0xDB][0]
@@ -41,7 +41,7 @@ def test_plan_verdicts():
         s = [(m, bytearray(p)) for m, p in segs]
         fn(s)
         return _join(s)
-    U, M = ops.JPEG_UNSUPPORTED, ops.JPEG_MALFORMED
+    U, M = decode.UNSUPPORTED, decode.MALFORMED
     # unsupported: decoded on the host with PIL
     prog = [f for f in _fixtures() if f[0] == "53x37_progressive"][0][1]
     assert _verdict(prog) == (U, "progressive")
@@ -89,28 +89,28 @@ def test_plan_verdicts():
     cut = base[:len(base) // 2]
     assert _verdict(cut) == (M, "scan does not end in a marker inside the buffer")
     # one batch: every verdict on its own image, the supported ones packed
-    plan = ops.JpegPlan([base, cut, prog, base], pin=False, fallback=False)
+    plan = decode.JpegPlan([base, cut, prog, base], pin=False, fallback=False)
     assert [v for v, _ in plan.verdicts()] == [0, 2, 1, 0]
     with pytest.raises(ValueError, match="image 1"):
         plan.check()
 
 
 def test_host_decode_equals_fixtures():
-    from litemkd_amd import ops
+    from litemkd_amd import decode
     fx = _fixtures()
-    imgs, plan, status = ops.jpeg_decode_host([f[1] for f in fx])
+    imgs, plan, status = decode.jpeg_decode_host([f[1] for f in fx])
     assert not status.any()
     for (name, _, ref), img, (v, why) in zip(fx, imgs, plan.verdicts()):
         if name.endswith("progressive"):
-            assert img is None and v == ops.JPEG_UNSUPPORTED, name
+            assert img is None and v == decode.UNSUPPORTED, name
             continue
-        assert v == ops.JPEG_SUPPORTED, (name, why)
+        assert v == decode.SUPPORTED, (name, why)
         assert np.array_equal(img, ref), (name, int((img != ref).sum()))
 
 
 def test_host_decode_equals_pil_random():
     Image = pytest.importorskip("PIL.Image")
-    from litemkd_amd import ops
+    from litemkd_amd import decode
     g = np.random.default_rng(1234)
     blobs = []
     for _ in range(40):
@@ -124,20 +124,20 @@ def test_host_decode_equals_pil_random():
         b = io.BytesIO()
         Image.fromarray(a.astype(np.uint8)).save(b, "JPEG", **kw)
         blobs.append(b.getvalue())
-    imgs, plan, status = ops.jpeg_decode_host(blobs)
+    imgs, plan, status = decode.jpeg_decode_host(blobs)
     assert not status.any()
     for b, img in zip(blobs, imgs):
         assert np.array_equal(img, np.array(Image.open(io.BytesIO(b))))
 
 
 def test_host_decode_flags_altered_scan():
-    from litemkd_amd import ops
+    from litemkd_amd import decode
     base = _baseline()
     sos = base.index(b"\xff\xda")
     mid = (sos + len(base)) // 2
     bad = base[:mid] + b"\xff\xd9" + base[mid + 2:]            # the scan now ends half way: the decoder runs out of data
-    imgs, plan, status = ops.jpeg_decode_host([base, bad, base])
-    assert list(plan.verdicts()[1]) == [ops.JPEG_SUPPORTED, "supported"]
+    imgs, plan, status = decode.jpeg_decode_host([base, bad, base])
+    assert list(plan.verdicts()[1]) == [decode.SUPPORTED, "supported"]
     assert status[0] == 0 and status[1] != 0 and status[2] == 0
     with pytest.raises(ValueError, match="image 1"):
         plan.raise_on_status(status)
@@ -148,13 +148,13 @@ def test_corruption_matrix():
     through the flat host twin and through the entropy launch's own windowed program run lane by lane.  JPEG has no checksum: a flip
     that leaves the Huffman stream decodable to the right number of blocks is not flagged (13 % to 79 % of the flips of a fixture,
     55 % over the matrix), so an unflagged case has to decode to exactly what libjpeg decodes with its C IDCT (jidctint.c)."""
-    from litemkd_amd import ops
+    from litemkd_amd import decode
     cases = U.full_matrix()
     rst = U.renumbered_rst()
     good = U.fixture("53x37_ss1_q95")
     blobs = [c[1] for c in cases] + [rst[1], good[1]]
-    imgs, plan, status = ops.jpeg_decode_host(blobs, fallback=False)
-    wimgs, wplan, wstatus = ops.jpeg_decode_host(blobs, windowed=True, fallback=False)
+    imgs, plan, status = decode.jpeg_decode_host(blobs, fallback=False)
+    wimgs, wplan, wstatus = decode.jpeg_decode_host(blobs, windowed=True, fallback=False)
     verdicts = plan.verdicts()
     assert wplan.verdicts() == verdicts
     # the windowed twin: the flat twin's status on every case, its pixels wherever the status is 0
@@ -163,16 +163,16 @@ def test_corruption_matrix():
         if a is not None and s == 0:
             assert np.array_equal(a, b), k
     # the good image is untouched
-    assert verdicts[-1] == (ops.JPEG_SUPPORTED, "supported") and status[-1] == 0
+    assert verdicts[-1] == (decode.SUPPORTED, "supported") and status[-1] == 0
     assert np.array_equal(imgs[-1], good[2]) and np.array_equal(wimgs[-1], good[2])
     # the renumbered RST
-    assert verdicts[-2][0] == ops.JPEG_SUPPORTED and status[-2] == 4, (verdicts[-2], status[-2])
+    assert verdicts[-2][0] == decode.SUPPORTED and status[-2] == 4, (verdicts[-2], status[-2])
     seen, unflagged, deep = {}, [], 0
     for k, ((label, data), (v, why), s) in enumerate(zip(cases, verdicts, status.tolist())):
-        assert v in (ops.JPEG_SUPPORTED, ops.JPEG_MALFORMED) or (v, why) == (ops.JPEG_UNSUPPORTED, "more than one scan"), (label, v, why)
+        assert v in (decode.SUPPORTED, decode.MALFORMED) or (v, why) == (decode.UNSUPPORTED, "more than one scan"), (label, v, why)
         if label.startswith("321x239") and "flip@" in label and U.offset_of(label) > 8192:
             deep += 1
-        if v != ops.JPEG_SUPPORTED:
+        if v != decode.SUPPORTED:
             assert s == 0, label
             seen["plan"] = seen.get("plan", 0) + 1
         elif s:
@@ -181,7 +181,7 @@ def test_corruption_matrix():
         else:
             unflagged.append(k)
         if "cut@" in label:
-            assert v == ops.JPEG_SUPPORTED and s == 3, (label, v, s)      # a cut scan ends early
+            assert v == decode.SUPPORTED and s == 3, (label, v, s)      # a cut scan ends early
     print("corruption matrix: %d cases, flagged %s, unflagged %d, beyond the first window %d" % (len(cases), seen, len(unflagged), deep))
     assert {1, 2, 3, 5} <= set(seen), seen
     flagged = len(cases) - len(unflagged)
@@ -199,11 +199,11 @@ def test_unsupported_image_that_pil_refuses_is_named():
     """a flip that plants a marker inside the scan makes the plan's verdict 'unsupported: more than one scan'; the image goes to PIL,
     and where PIL refuses it too the error is the ValueError every other damaged image raises, naming the image"""
     from PIL import Image
-    from litemkd_amd import ops
+    from litemkd_amd import decode
     import _png_util as PU
     cases = U.corruption_matrix("53x37_ss2_q75", flips=300, seed=0)
-    plan = ops.JpegPlan([c[1] for c in cases], pin=False, fallback=False)
-    un = [k for k, (v, why) in enumerate(plan.verdicts()) if v == ops.JPEG_UNSUPPORTED]
+    plan = decode.JpegPlan([c[1] for c in cases], pin=False, fallback=False)
+    un = [k for k, (v, why) in enumerate(plan.verdicts()) if v == decode.UNSUPPORTED]
     assert len(un) == 3 and all(plan.verdicts()[k][1] == "more than one scan" for k in un)
 
     def pil_error(data):
@@ -220,24 +220,24 @@ def test_unsupported_image_that_pil_refuses_is_named():
     for k in un:
         blobs, names = [good, cases[k][1], good], ["a.jpg", "b.jpg", "c.jpg"]
         if errors[k] is None:
-            p = ops.JpegPlan(blobs, names=names, pin=False)
+            p = decode.JpegPlan(blobs, names=names, pin=False)
             assert sorted(p.fallback) == [1] and p.fallback[1].shape == (37, 53, 3)
             continue
         with pytest.raises(ValueError) as ei:
-            ops.JpegPlan(blobs, names=names, pin=False)
+            decode.JpegPlan(blobs, names=names, pin=False)
         assert "JPEG image 1 (b.jpg) is malformed" in str(ei.value) and str(errors[k]) in str(ei.value), str(ei.value)
         assert isinstance(ei.value.__cause__, OSError) and str(ei.value.__cause__) == str(errors[k])
         with pytest.raises(ValueError, match=r"JPEG image 1 is malformed: PIL refuses it"):
-            ops.jpeg_decode_host(blobs)
+            decode.jpeg_decode_host(blobs)
     # PngPlan shares the fallback: an interlaced file (unsupported) whose stream is cut short
     lace = PU.fixture("17x9_interlaced")[1]
     z = PU.stream_of(lace)
     cut = PU.with_stream(lace, z[:len(z) // 2])
-    assert ops.PngPlan([cut], pin=False, fallback=False).verdicts()[0] == (ops.PNG_UNSUPPORTED, "Adam7 interlace")
+    assert decode.PngPlan([cut], pin=False, fallback=False).verdicts()[0] == (decode.UNSUPPORTED, "Adam7 interlace")
     err = pil_error(cut)
     assert err is not None
     with pytest.raises(ValueError) as ei:
-        ops.PngPlan([PU.fixture("53x37_t2_mix")[1], cut], names=["a.png", "b.png"], pin=False)
+        decode.PngPlan([PU.fixture("53x37_t2_mix")[1], cut], names=["a.png", "b.png"], pin=False)
     assert "PNG image 1 (b.png) is malformed" in str(ei.value) and str(err) in str(ei.value), str(ei.value)
     assert isinstance(ei.value.__cause__, OSError)
 

@@ -1,5 +1,5 @@
 """Writes tests/golden/jpeg/fixtures.npz: JPEG files of synthetic images written with PIL, and PIL's decode of each
-(PIL.Image.open(f).load(), the reference's read_single_image, video_reader.py:334-343) - the expected output of ops.jpeg_decode.
+(PIL.Image.open(f).load(), the reference's read_single_image, video_reader.py:334-343) - the expected output of decode.jpeg_decode.
 
     python tools/gen_jpeg_golden.py
     python tools/gen_jpeg_golden.py --dump DIR      (writes the committed fixtures out as DIR/<name>.jpg)

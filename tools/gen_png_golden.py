@@ -1,5 +1,5 @@
 """Writes tests/golden/png/fixtures.npz: PNG files and PIL's decode of each (PIL.Image.open(f).convert("RGB"), the teacher-side readers'
-read_single_image, AuxDataset.py:129-136) - the expected output of ops.png_decode.
+read_single_image, AuxDataset.py:129-136) - the expected output of decode.png_decode.
 
     python tools/gen_png_golden.py
     python tools/gen_png_golden.py --dump DIR      (writes the committed fixtures out as DIR/<name>.png)

@@ -4,7 +4,7 @@
 
 A seeded dataset of 320x240 4:2:0 frames at quality 75 and 90 (typical extracted frames), written with PIL under a temporary directory.
 Reports, per quality:
-  * decode_ms_per_400_frames: ops.jpeg_decode of one 400-frame batch (upload + three launches), device events, after warm-up;
+  * decode_ms_per_400_frames: decode.jpeg_decode of one 400-frame batch (upload + three launches), device events, after warm-up;
   * plan_ms_per_400_frames: the host half (lmkd_jpeg_plan + packing), and host_episode_ms: JpegFrameEpisodes.host_episode() - file reads,
     plan, draws, features - what the prefetch thread does per 5-way 5-shot episode;
   * pil_ms_per_400_frames_16_threads: PIL decoding the same 400 frames on 16 host threads;
@@ -48,14 +48,14 @@ def encode(img, q):
 
 
 def decode_bench(blobs, reps=20):
-    from litemkd_amd import ops
+    from litemkd_amd import decode
     for _ in range(3):
-        ops.jpeg_decode(blobs, check=False)
+        decode.jpeg_decode(blobs, check=False)
     torch.cuda.synchronize()
-    plans = [ops.JpegPlan(blobs) for _ in range(2)]
+    plans = [decode.JpegPlan(blobs) for _ in range(2)]
     t0 = time.perf_counter()
     for _ in range(reps):
-        ops.JpegPlan(blobs, fallback=False)
+        decode.JpegPlan(blobs, fallback=False)
     plan_ms = (time.perf_counter() - t0) / reps * 1e3
     out = torch.empty((len(blobs), 240, 320, 3), dtype=torch.uint8, device="cuda")
     s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -162,10 +162,10 @@ def main():
             ds = JpegFrameEpisodes(cfg, os.path.join(tmp, "jpg"), teacher_path=os.path.join(tmp, "feat"), device="cuda")
             random.seed(0)
             for _ in range(4):
-                ds.host_episode()["jpeg"].release()
+                ds.host_episode()["plan"].release()
             t0 = time.perf_counter()
             for _ in range(16):
-                ds.host_episode()["jpeg"].release()
+                ds.host_episode()["plan"].release()
             res["host_episode_ms"] = (time.perf_counter() - t0) / 16 * 1e3
             rates = {"jpeg": [], "npy": []}
             for _ in range(a.repeats):

@@ -39,17 +39,17 @@ def encode_png(img):
 
 
 def decode_bench(blobs, reps):
-    from litemkd_amd import ops
+    from litemkd_amd import decode
     for _ in range(3):
-        ops.png_decode(blobs, check=False)
+        decode.png_decode(blobs, check=False)
     torch.cuda.synchronize()
-    frames, status = ops.png_decode(blobs, check=False)
-    if int(status.cpu().abs().sum()) or ops.png_stats()["fallback"]:
+    frames, status = decode.png_decode(blobs, check=False)
+    if int(status.cpu().abs().sum()) or decode.png_stats()["fallback"]:
         raise RuntimeError("the benchmark's frames must all decode on the GPU")
-    plans = [ops.PngPlan(blobs) for _ in range(2)]
+    plans = [decode.PngPlan(blobs) for _ in range(2)]
     t0 = time.perf_counter()
     for _ in range(max(3, reps // 4)):
-        ops.PngPlan(blobs, fallback=False)
+        decode.PngPlan(blobs, fallback=False)
     plan_ms = (time.perf_counter() - t0) / max(3, reps // 4) * 1e3
     out = torch.empty((len(blobs), 240, 320, 3), dtype=torch.uint8, device="cuda")
     s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
