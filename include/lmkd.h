@@ -534,8 +534,10 @@ int lmkd_strm_attn_fwd(const float* x, const float* qkv, const float* gamma, flo
 int lmkd_strm_attn_bwd(const float* dy, const float* qkv, const float* probs, const float* gamma, float* dqkv, float* dgamma_part,
                        float* dgamma, int F, int C, void* stream);
 /* MLP_Mix_Enrich.forward (:185-202) up to residual2: xp [V,L,D] = (x + pe [L,D]) * mask (nullable), y = W2 relu(W1 xp + b1) + b2 + xp
-   along the frame axis (W1, W2 [L,L], L == 8); hmask (nullable) [V,L,D] = 1 where hidden unit k of (video, channel) is active.  Backward: dx, dparams [144] = dW1 | db1 | dW2 | db2 through part
-   [lmkd_strm_tokmlp_parts(V, D)][144] per-workgroup partial rows. */
+   along the frame axis (W1, W2 [L,L], 2 <= L <= 16: L == 8 on its own kernels, every other length on an instance of a family templated
+   on L with the same arithmetic); hmask (nullable) [V,L,D] = 1 where hidden unit k of (video, channel) is active.  Backward: dx,
+   dparams [2 L^2 + 2 L] = dW1 | db1 | dW2 | db2 (144 floats at L == 8, 544 at L == 16) through part
+   [lmkd_strm_tokmlp_parts(V, D)][2 L^2 + 2 L] per-workgroup partial rows; the row count does not depend on L. */
 long lmkd_strm_tokmlp_parts(long V, int D);
 int lmkd_strm_tokmlp_fwd(const float* x, const float* pe, const float* mask, const float* w1, const float* b1, const float* w2, const float* b2,
                          float* xp, float* y, unsigned char* hmask, int V, int L, int D, void* stream);
@@ -546,9 +548,12 @@ int lmkd_strm_tokmlp_bwd(const float* dy, const float* xp, const float* mask, co
 int lmkd_strm_pair_embed(const float* P, const float* bias, float* E, int NV, int L, int Hd, void* stream);
 /* rows of E: Ns support videos, then Nq query videos.  order [Ns]: support video of class-sorted position c * shot + m.  dist / idx
    [Nq * T][way]: minimum over the class's shot * T rows of sqrt(sum (q - s)^2) and its row m * T + t (first smallest);
-   logits [Nq][way] = - mean over the T pair rows.  Hd == 1024. */
+   logits [Nq][way] = - mean over the T pair rows.  Hd == 1024, 2 <= L <= 16.  Two kernels give the same bits: one wave per (4 query
+   rows, class) reading the class's support rows from global memory (every L <= 8), and one workgroup per (16 query rows, class) that
+   passes them through LDS once (L > 8 in the measured dispatch). */
 int lmkd_strm_patchdist_fwd(const float* E, const int* order, float* dist, int* idx, float* logits, int Ns, int Nq, int way, int shot, int L,
                             int Hd, void* stream);
+int lmkd_patchdist_set_tiled(int mode); /* A/B runs and tests, process-wide: -1 (default) = the measured dispatch above, 0 = never the tiled kernel, 1 = always, also at L <= 8; other values are refused */
 /* g [Nq][way], pos [Ns] = class-sorted position of each support video -> dpre [NV * T][Hd] (gradient before the ReLU) and
    dP [NV * L][2 Hd]; distance 0 gives gradient 0 */
 int lmkd_strm_patchdist_bwd(const float* E, const int* order, const int* pos, const float* dist, const int* idx, const float* g, float* dpre,

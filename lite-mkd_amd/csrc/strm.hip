@@ -5,7 +5,7 @@
 //                    applied in the same launch, and the arg-max byte per output; backward is a gather over the windows of a pixel
 //   patch attention  per frame: energy = Q K^T (unscaled, 16 x 16 dot products of C terms), row softmax, out = attn V, y = gamma out + x;
 //                    backward gives dQ | dK | dV in one [F,16,3C] block and one dgamma partial per frame
-//   token MLP        per video and channel over the 8 frames: y = W2 relu(W1 xp + b1) + b2 + xp with xp = (x + pe) * mask
+//   token MLP        per video and channel over the L frames (2 <= L <= 16): y = W2 relu(W1 xp + b1) + b2 + xp with xp = (x + pe) * mask
 //   patch distance   DistanceLoss: relu(P_a[i] + P_b[j] + b) per frame pair, the minimum Euclidean distance of every query pair row to the
 //                    pair rows of each class in the difference form sum (q - s)^2, the arg-min, the mean over the pairs, negated
 //
@@ -18,10 +18,12 @@
 #define ST_NP 16           // patches per frame (4 x 4)
 #define ST_KC 256          // columns of Q / K staged in LDS per step of the energy products
 #define ST_LD (ST_KC + 4)  // row stride of the staged tiles: consecutive rows start 4 banks apart, so 16 rows read 16 distinct 16-byte slots
-#define ST_L 8             // frames per video of the token MLP (args.seq_len of every configuration of the reference)
+#define ST_L 8             // frames per video of the token MLP's own kernels (args.seq_len of every configuration of the reference)
+#define ST_LMAX 16         // longest clip of the templated token-MLP family and of the patch-distance head
 #define ST_TOK 144         // token-MLP parameter gradients: dW1 [8][8] | db1 [8] | dW2 [8][8] | db2 [8]
 #define ST_HD 1024         // width of DistanceLoss.clsW's output
-#define ST_QR 4            // query pair rows per wave of the minimum-distance kernel
+#define ST_QR 4            // query pair rows per wave of the minimum-distance kernels
+#define ST_SB 8            // support pair rows per LDS block of the tiled minimum-distance kernel (4 KB each)
 
 static inline int st_grid(long n) { return (int)((n + ST_THREADS - 1) / ST_THREADS); }
 __device__ __forceinline__ float4 sld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
@@ -410,27 +412,190 @@ __global__ __launch_bounds__(ST_THREADS) void strm_tokmlp_bwd_k(const float* __r
   }
 }
 
+// The same two kernels for every other clip length 2 <= L <= ST_LMAX (args.seq_len up to 16, as the MFM teacher takes): L is a template
+// argument, so the per-lane arrays a / h / g / dh [L] stay in registers; the form (one lane per (video, channel), both L x L weights and
+// the biases in LDS) and the arithmetic (fmaf chains in index order, (acc + b2) + a) are those of the 8-frame kernels above, which
+// L == 8 keeps.
+template <int L>
+struct TokWL {
+  float w1[L][L], b1[L], w2[L][L], b2[L];
+};
+template <int L>
+__device__ __forceinline__ void tok_load_l(TokWL<L>* s, const float* w1, const float* b1, const float* w2, const float* b2) {
+  const int t = threadIdx.x;
+  static_assert(L * L <= ST_THREADS, "one weight per lane");
+  if (t < L * L) {
+    (&s->w1[0][0])[t] = w1[t];
+    (&s->w2[0][0])[t] = w2[t];
+  }
+  if (t < L) {
+    s->b1[t] = b1[t];
+    s->b2[t] = b2[t];
+  }
+  __syncthreads();
+}
+
+template <int L>
+__global__ __launch_bounds__(ST_THREADS) void strm_tokmlp_fwd_l_k(const float* __restrict__ x, const float* __restrict__ pe,
+                                                                   const float* __restrict__ mask, const float* __restrict__ w1,
+                                                                   const float* __restrict__ b1, const float* __restrict__ w2,
+                                                                   const float* __restrict__ b2, float* __restrict__ xp,
+                                                                   float* __restrict__ y, unsigned char* __restrict__ hmask, long V, int D) {
+  __shared__ TokWL<L> s;
+  tok_load_l<L>(&s, w1, b1, w2, b2);
+  const long t = (long)blockIdx.x * ST_THREADS + threadIdx.x;
+  if (t >= V * D) return;
+  const long v = t / D;
+  const int d = (int)(t % D);
+  float a[L], h[L];
+#pragma unroll
+  for (int l = 0; l < L; ++l) {
+    const long at = (v * L + l) * D + d;
+    float u = x[at] + pe[l * D + d];
+    if (mask) u *= mask[at];
+    a[l] = u;
+    xp[at] = u;
+  }
+#pragma unroll
+  for (int k = 0; k < L; ++k) {
+    float acc = 0.f;
+#pragma unroll
+    for (int l = 0; l < L; ++l) acc = fmaf(s.w1[k][l], a[l], acc);
+    h[k] = fmaxf(acc + s.b1[k], 0.f);
+    if (hmask) hmask[(v * L + k) * D + d] = h[k] > 0.f;
+  }
+#pragma unroll
+  for (int o = 0; o < L; ++o) {
+    float acc = 0.f;
+#pragma unroll
+    for (int k = 0; k < L; ++k) acc = fmaf(s.w2[o][k], h[k], acc);
+    y[(v * L + o) * D + d] = (acc + s.b2[o]) + a[o];
+  }
+}
+
+// part[blockIdx.x][dW1 [L][L] | db1 [L] | dW2 [L][L] | db2 [L]]: 2 L^2 + 2 L outputs (544 at L = 16) over 256 lanes, so lane t reduces
+// outputs t, t + 256, t + 512 one after the other, each over the 256 staged lanes in lane order.  The staging rows carry one pad float:
+// lanes that reduce different rows at the same position then read different LDS banks (unpadded, every row starts on bank 0).
+template <int L>
+__global__ __launch_bounds__(ST_THREADS) void strm_tokmlp_bwd_l_k(const float* __restrict__ dy, const float* __restrict__ xp,
+                                                                   const float* __restrict__ mask, const float* __restrict__ w1,
+                                                                   const float* __restrict__ b1, const float* __restrict__ w2,
+                                                                   float* __restrict__ dx, float* __restrict__ part, long V, int D) {
+  constexpr int NT = 2 * L * L + 2 * L;
+  __shared__ TokWL<L> s;
+  __shared__ float st[4][L][ST_THREADS + 1];      // dy | h | masked dh | xp of every lane
+  tok_load_l<L>(&s, w1, b1, w2, b1);
+  const int tid = threadIdx.x;
+  const long t = (long)blockIdx.x * ST_THREADS + tid;
+  const bool live = t < V * D;
+  const long v = live ? t / D : 0;
+  const int d = live ? (int)(t % D) : 0;
+  float a[L], h[L], g[L], dh[L];
+#pragma unroll
+  for (int l = 0; l < L; ++l) {
+    const long at = (v * L + l) * D + d;
+    a[l] = live ? xp[at] : 0.f;
+    g[l] = live ? dy[at] : 0.f;
+  }
+#pragma unroll
+  for (int k = 0; k < L; ++k) {
+    float acc = 0.f;
+#pragma unroll
+    for (int l = 0; l < L; ++l) acc = fmaf(s.w1[k][l], a[l], acc);
+    h[k] = live ? fmaxf(acc + s.b1[k], 0.f) : 0.f;
+  }
+#pragma unroll
+  for (int k = 0; k < L; ++k) {
+    float acc = 0.f;
+#pragma unroll
+    for (int o = 0; o < L; ++o) acc = fmaf(s.w2[o][k], g[o], acc);
+    dh[k] = h[k] > 0.f ? acc : 0.f;
+  }
+#pragma unroll
+  for (int l = 0; l < L; ++l) {
+    float acc = 0.f;
+#pragma unroll
+    for (int k = 0; k < L; ++k) acc = fmaf(s.w1[k][l], dh[k], acc);
+    if (live) {
+      const long at = (v * L + l) * D + d;
+      float r = g[l] + acc;
+      if (mask) r *= mask[at];
+      dx[at] = r;
+    }
+    st[0][l][tid] = g[l];
+    st[1][l][tid] = h[l];
+    st[2][l][tid] = dh[l];
+    st[3][l][tid] = a[l];
+  }
+  __syncthreads();
+  for (int o = tid; o < NT; o += ST_THREADS) {
+    const float *u, *w = nullptr;
+    if (o < L * L) {      // dW1[k][l] = sum dh_k xp_l
+      u = st[2][o / L];
+      w = st[3][o % L];
+    } else if (o < L * L + L) {      // db1[k]
+      u = st[2][o - L * L];
+    } else if (o < 2 * L * L + L) {      // dW2[o][k] = sum dy_o h_k
+      u = st[0][(o - L * L - L) / L];
+      w = st[1][(o - L * L - L) % L];
+    } else {      // db2[o]
+      u = st[0][o - 2 * L * L - L];
+    }
+    float acc = 0.f;
+    if (w)
+      for (int i = 0; i < ST_THREADS; ++i) acc = fmaf(u[i], w[i], acc);
+    else
+      for (int i = 0; i < ST_THREADS; ++i) acc += u[i];
+    part[(long)blockIdx.x * NT + o] = acc;
+  }
+}
+
+#define ST_L_CASE(N, ...)    \
+  case N: {                  \
+    constexpr int Lc = N;    \
+    __VA_ARGS__;             \
+  } break;
+// every clip length but 8 (which has its own kernels): Lc is the compile-time length inside the statement
+#define ST_DISPATCH_L(LV, ...)                                                                                                        \
+  switch (LV) {                                                                                                                       \
+    ST_L_CASE(2, __VA_ARGS__) ST_L_CASE(3, __VA_ARGS__) ST_L_CASE(4, __VA_ARGS__) ST_L_CASE(5, __VA_ARGS__) ST_L_CASE(6, __VA_ARGS__)  \
+    ST_L_CASE(7, __VA_ARGS__) ST_L_CASE(9, __VA_ARGS__) ST_L_CASE(10, __VA_ARGS__) ST_L_CASE(11, __VA_ARGS__)                          \
+    ST_L_CASE(12, __VA_ARGS__) ST_L_CASE(13, __VA_ARGS__) ST_L_CASE(14, __VA_ARGS__) ST_L_CASE(15, __VA_ARGS__)                        \
+    ST_L_CASE(16, __VA_ARGS__)                                                                                                        \
+    default: break;                                                                                                                   \
+  }
+
 extern "C" long lmkd_strm_tokmlp_parts(long V, int D) { return V > 0 && D > 0 ? (V * D + ST_THREADS - 1) / ST_THREADS : 0; }
 
 extern "C" int lmkd_strm_tokmlp_fwd(const float* x, const float* pe, const float* mask, const float* w1, const float* b1, const float* w2,
                                     const float* b2, float* xp, float* y, unsigned char* hmask, int V, int L, int D, void* stream) {
   LMKD_REQUIRE(x && pe && w1 && b1 && w2 && b2 && xp && y && V > 0 && D > 0, "lmkd_strm_tokmlp_fwd: bad arguments");
-  LMKD_REQUIRE(L == ST_L, "lmkd_strm_tokmlp_fwd: the token MLP is built for %d frames per video, got %d", ST_L, L);
-  hipLaunchKernelGGL(strm_tokmlp_fwd_k, dim3(st_grid((long)V * D)), dim3(ST_THREADS), 0, (hipStream_t)stream, x, pe, mask, w1, b1, w2, b2, xp,
-                     y, hmask, (long)V, D);
+  LMKD_REQUIRE(L >= 2 && L <= ST_LMAX, "lmkd_strm_tokmlp_fwd: the token MLP takes 2 <= L <= %d frames per video, got %d", ST_LMAX, L);
+  const dim3 grid(st_grid((long)V * D));
+  if (L == ST_L) {
+    hipLaunchKernelGGL(strm_tokmlp_fwd_k, grid, dim3(ST_THREADS), 0, (hipStream_t)stream, x, pe, mask, w1, b1, w2, b2, xp, y, hmask, (long)V, D);
+  } else {
+    ST_DISPATCH_L(L, hipLaunchKernelGGL((strm_tokmlp_fwd_l_k<Lc>), grid, dim3(ST_THREADS), 0, (hipStream_t)stream, x, pe, mask, w1, b1, w2, b2,
+                                         xp, y, hmask, (long)V, D));
+  }
   LMKD_CHECK_LAUNCH("strm_tokmlp_fwd_k");
   return LMKD_OK;
 }
 
-/* dparams [144] = dW1 | db1 | dW2 | db2; part: lmkd_strm_tokmlp_parts(V, D) rows of 144 floats */
+/* dparams [2 L^2 + 2 L] = dW1 | db1 | dW2 | db2; part: lmkd_strm_tokmlp_parts(V, D) rows of 2 L^2 + 2 L floats */
 extern "C" int lmkd_strm_tokmlp_bwd(const float* dy, const float* xp, const float* mask, const float* w1, const float* b1, const float* w2,
                                     float* dx, float* part, float* dparams, int V, int L, int D, void* stream) {
   LMKD_REQUIRE(dy && xp && w1 && b1 && w2 && dx && part && dparams && V > 0 && D > 0, "lmkd_strm_tokmlp_bwd: bad arguments");
-  LMKD_REQUIRE(L == ST_L, "lmkd_strm_tokmlp_bwd: the token MLP is built for %d frames per video, got %d", ST_L, L);
-  const int nb = st_grid((long)V * D);
-  hipLaunchKernelGGL(strm_tokmlp_bwd_k, dim3(nb), dim3(ST_THREADS), 0, (hipStream_t)stream, dy, xp, mask, w1, b1, w2, dx, part, (long)V, D);
+  LMKD_REQUIRE(L >= 2 && L <= ST_LMAX, "lmkd_strm_tokmlp_bwd: the token MLP takes 2 <= L <= %d frames per video, got %d", ST_LMAX, L);
+  const int nb = st_grid((long)V * D), nt = 2 * L * L + 2 * L;
+  if (L == ST_L) {
+    hipLaunchKernelGGL(strm_tokmlp_bwd_k, dim3(nb), dim3(ST_THREADS), 0, (hipStream_t)stream, dy, xp, mask, w1, b1, w2, dx, part, (long)V, D);
+  } else {
+    ST_DISPATCH_L(L, hipLaunchKernelGGL((strm_tokmlp_bwd_l_k<Lc>), dim3(nb), dim3(ST_THREADS), 0, (hipStream_t)stream, dy, xp, mask, w1, b1, w2,
+                                         dx, part, (long)V, D));
+  }
   LMKD_CHECK_LAUNCH("strm_tokmlp_bwd_k");
-  hipLaunchKernelGGL(strm_reduce_rows_k, dim3(ST_TOK), dim3(ST_THREADS), 0, (hipStream_t)stream, part, dparams, nb, ST_TOK);
+  hipLaunchKernelGGL(strm_reduce_rows_k, dim3(nt), dim3(ST_THREADS), 0, (hipStream_t)stream, part, dparams, nb, nt);
   LMKD_CHECK_LAUNCH("strm_reduce_rows_k");
   return LMKD_OK;
 }
@@ -516,6 +681,107 @@ __global__ __launch_bounds__(64) void strm_mindist_k(const float* __restrict__ E
         dist[(long)(r0 + r) * way + c] = sqrtf(best[r]);
         idx[(long)(r0 + r) * way + c] = bi[r];
       }
+  }
+}
+
+// The same minimum for long clips (the work grows with T^2): one workgroup of four waves per (4 ST_QR = 16 query pair rows, class).  Wave w
+// keeps query rows 4 w .. 4 w + 3 in registers as above; the class's support pair rows pass through LDS in blocks of ST_SB rows, so a row
+// is fetched from global memory once per workgroup and read from LDS once per wave.  The distance of one (query row, support row) is the
+// arithmetic of strm_mindist_k: direct differences, lane l on columns 4 l + 256 m, one fmaf chain over m per component,
+// (x + y) + (z + w), and the xor butterfly 32, 16, .. 1.  The butterfly runs transposed over the 8 sums of (4 query rows, 2 support rows):
+// at offsets 32, 16 and 8 a lane keeps half of its sums and hands the other half to its partner, which adds the same two operands the
+// plain butterfly adds (own + partner's, in either order), so after three steps lanes 8 j .. 8 j + 7 hold sum j = 2 r + s reduced over
+// offsets 32, 16, 8 and three ordinary steps finish it: 10 exchanges for 8 sums instead of 48, the same tree, the same bits.  Candidates
+// are then visited in (member, t) order with strict <, every lane of query row r's 16 lanes alike.
+__global__ __launch_bounds__(ST_THREADS) void strm_mindist_tile_k(const float* __restrict__ E, const int* __restrict__ order,
+                                                                   float* __restrict__ dist, int* __restrict__ idx, int Ns, int Nq, int way,
+                                                                   int shot, int T) {
+  __shared__ __attribute__((aligned(16))) float S[ST_SB][ST_HD];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c = blockIdx.y;
+  const int R = Nq * T, r0 = blockIdx.x * (4 * ST_QR) + wave * ST_QR, NS = shot * T;
+  float4 q[ST_QR][4];
+#pragma unroll
+  for (int r = 0; r < ST_QR; ++r) {
+    const int row = min(r0 + r, R - 1);
+    const float* e = E + ((long)Ns * T + row) * ST_HD + lane * 4;
+#pragma unroll
+    for (int m = 0; m < 4; ++m) q[r][m] = sld4(e + m * 256);
+  }
+  float best = INFINITY;      // of query row r0 + (lane >> 4)
+  int bi = 0;
+  const bool up32 = lane & 32, up16 = lane & 16, up8 = lane & 8;
+  for (int g0 = 0; g0 < NS; g0 += ST_SB) {
+    const int nb = min(ST_SB, NS - g0);
+    __syncthreads();      // the previous block has been read by every wave
+    for (int b = 0; b < nb; ++b) {
+      const int g = g0 + b, sv = order[c * shot + g / T];
+      sst4(&S[b][tid * 4], sld4(E + ((long)sv * T + g % T) * ST_HD + tid * 4));
+    }
+    __syncthreads();
+    for (int b = 0; b < nb; b += 2) {
+      const bool two = b + 1 < nb;
+      const float* s0 = &S[b][lane * 4];
+      const float* s1 = &S[two ? b + 1 : b][lane * 4];
+      float4 a[ST_QR][2];
+#pragma unroll
+      for (int r = 0; r < ST_QR; ++r) a[r][0] = a[r][1] = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+      for (int m = 0; m < 4; ++m) {
+        const float4 u0 = sld4(s0 + m * 256), u1 = sld4(s1 + m * 256);
+#pragma unroll
+        for (int r = 0; r < ST_QR; ++r) {
+          {
+            const float dx = q[r][m].x - u0.x, dy = q[r][m].y - u0.y, dz = q[r][m].z - u0.z, dw = q[r][m].w - u0.w;
+            a[r][0].x = fmaf(dx, dx, a[r][0].x);
+            a[r][0].y = fmaf(dy, dy, a[r][0].y);
+            a[r][0].z = fmaf(dz, dz, a[r][0].z);
+            a[r][0].w = fmaf(dw, dw, a[r][0].w);
+          }
+          {
+            const float dx = q[r][m].x - u1.x, dy = q[r][m].y - u1.y, dz = q[r][m].z - u1.z, dw = q[r][m].w - u1.w;
+            a[r][1].x = fmaf(dx, dx, a[r][1].x);
+            a[r][1].y = fmaf(dy, dy, a[r][1].y);
+            a[r][1].z = fmaf(dz, dz, a[r][1].z);
+            a[r][1].w = fmaf(dw, dw, a[r][1].w);
+          }
+        }
+      }
+      float v8[8];      // sum j = 2 r + s
+#pragma unroll
+      for (int r = 0; r < ST_QR; ++r)
+#pragma unroll
+        for (int s = 0; s < 2; ++s) v8[2 * r + s] = (a[r][s].x + a[r][s].y) + (a[r][s].z + a[r][s].w);
+      float v4[4], v2[2];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {      // lanes 32.. keep sums 4..7
+        const float keep = up32 ? v8[k + 4] : v8[k], give = up32 ? v8[k] : v8[k + 4];
+        v4[k] = keep + __shfl_xor(give, 32, 64);
+      }
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        const float keep = up16 ? v4[k + 2] : v4[k], give = up16 ? v4[k] : v4[k + 2];
+        v2[k] = keep + __shfl_xor(give, 16, 64);
+      }
+      const float keep = up8 ? v2[1] : v2[0], give = up8 ? v2[0] : v2[1];
+      float d2 = keep + __shfl_xor(give, 8, 64);
+      for (int o = 4; o > 0; o >>= 1) d2 += __shfl_xor(d2, o, 64);
+      // this lane: query row lane >> 4, support row b + ((lane >> 3) & 1); the other support row's sum sits 8 lanes away
+      const float other = __shfl_xor(d2, 8, 64);
+      const float d0 = up8 ? other : d2, d1 = up8 ? d2 : other;
+      if (d0 < best) {
+        best = d0;
+        bi = g0 + b;
+      }
+      if (two && d1 < best) {
+        best = d1;
+        bi = g0 + b + 1;
+      }
+    }
+  }
+  const int row = r0 + (lane >> 4);
+  if ((lane & 15) == 0 && row < R) {
+    dist[(long)row * way + c] = sqrtf(best);
+    idx[(long)row * way + c] = bi;
   }
 }
 
@@ -611,14 +877,30 @@ extern "C" int lmkd_strm_pair_embed(const float* P, const float* bias, float* E,
   return LMKD_OK;
 }
 
+// which minimum-distance kernel lmkd_strm_patchdist_fwd launches: -1 = the measured dispatch, 0 = never the tiled one, 1 = always (A/B runs
+// and tests; both give the same bits)
+static int g_pd_tiled = -1;
+extern "C" int lmkd_patchdist_set_tiled(int mode) {
+  LMKD_REQUIRE(mode >= -1 && mode <= 1, "lmkd_patchdist_set_tiled: mode must be -1 (measured dispatch), 0 (never) or 1 (always), got %d", mode);
+  g_pd_tiled = mode;
+  return LMKD_OK;
+}
+
 extern "C" int lmkd_strm_patchdist_fwd(const float* E, const int* order, float* dist, int* idx, float* logits, int Ns, int Nq, int way, int shot,
                                        int L, int Hd, void* stream) {
   if (int rc = dist_check("lmkd_strm_patchdist_fwd", Ns, Nq, way, shot, L, Hd)) return rc;
   LMKD_REQUIRE(E && order && dist && idx && logits && aligned16(E), "lmkd_strm_patchdist_fwd: null or unaligned tensor");
   const int T = L * (L - 1) / 2;
-  hipLaunchKernelGGL(strm_mindist_k, dim3((Nq * T + ST_QR - 1) / ST_QR, way), dim3(64), 0, (hipStream_t)stream, E, order, dist, idx, Ns, Nq, way,
-                     shot, T);
-  LMKD_CHECK_LAUNCH("strm_mindist_k");
+  // measured dispatch (profiles/strm_long_bench.json): clips of up to 8 frames keep the one-wave kernel
+  if (g_pd_tiled == 1 || (g_pd_tiled < 0 && L > ST_L)) {
+    hipLaunchKernelGGL(strm_mindist_tile_k, dim3((Nq * T + 4 * ST_QR - 1) / (4 * ST_QR), way), dim3(ST_THREADS), 0, (hipStream_t)stream, E, order,
+                       dist, idx, Ns, Nq, way, shot, T);
+    LMKD_CHECK_LAUNCH("strm_mindist_tile_k");
+  } else {
+    hipLaunchKernelGGL(strm_mindist_k, dim3((Nq * T + ST_QR - 1) / ST_QR, way), dim3(64), 0, (hipStream_t)stream, E, order, dist, idx, Ns, Nq,
+                       way, shot, T);
+    LMKD_CHECK_LAUNCH("strm_mindist_k");
+  }
   hipLaunchKernelGGL(strm_dist_logits_k, dim3(st_grid((long)Nq * way)), dim3(ST_THREADS), 0, (hipStream_t)stream, dist, logits, Nq, way, T);
   LMKD_CHECK_LAUNCH("strm_dist_logits_k");
   return LMKD_OK;

@@ -3194,7 +3194,7 @@ class PatchMeanFn(torch.autograd.Function):
 
 
 def strm_tokmlp_fwd(x, pe, mask, w1, b1, w2, b2):
-    """x [V,8,D] -> (xp = (x + pe) * mask, y = W2 relu(W1 xp + b1) + b2 + xp along the frame axis)"""
+    """x [V,L,D], 2 <= L <= 16 -> (xp = (x + pe) * mask, y = W2 relu(W1 xp + b1) + b2 + xp along the frame axis)"""
     _strm_chk(x, pe, mask, w1, b1, w2, b2)
     V, L, D = x.shape
     xp, y = torch.empty_like(x), torch.empty_like(x)
@@ -3206,7 +3206,7 @@ def strm_tokmlp_fwd(x, pe, mask, w1, b1, w2, b2):
 
 
 def strm_tokmlp_bwd(dy, xp, mask, w1, b1, w2):
-    """-> (dx, dW1 [8,8], db1 [8], dW2 [8,8], db2 [8])"""
+    """-> (dx, dW1 [L,L], db1 [L], dW2 [L,L], db2 [L]): the library's dparams row is dW1 | db1 | dW2 | db2, 2 L^2 + 2 L floats"""
     _strm_chk(dy, xp, mask, w1, b1, w2)
     V, L, D = dy.shape
     dx = torch.empty_like(dy)
@@ -3258,6 +3258,12 @@ def strm_patchdist_embed(X, w, b, L):
     if STRM_TAPS is not None:
         STRM_TAPS.setdefault("relu", []).append(E > 0)
     return P, E
+
+
+def set_patchdist_tiled(mode):
+    """which minimum-distance kernel strm_patchdist_fwd launches, process-wide (lmkd_patchdist_set_tiled): -1 = the measured dispatch
+    (the LDS-tiled kernel for L > 8), 0 = never tiled, 1 = always tiled, also at L <= 8.  Both kernels give the same bits."""
+    lib().call("lmkd_patchdist_set_tiled", int(mode))
 
 
 def strm_patchdist_fwd(E, plan, Ns, Nq, L):

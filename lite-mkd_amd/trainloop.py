@@ -6,6 +6,7 @@
   * only the CE term carries the 1/16 accumulation scaling (distillers.py:326-335).
 wandb / checkpoint-file side effects are replaced by an optional `log` callback."""
 import itertools
+import math
 
 import numpy as np
 import torch
@@ -760,6 +761,10 @@ class GraphedEpisode:
             plan = ops.get_plan(pr[4], cfg.way)                    # built (H2D copies) outside the capture; the capture finds it cached
             plan.full_rowmap(pr[2].shape[0] + pr[3].shape[0])
             plan.full_rowmap(pr[0].shape[0] // cfg.seq_len + pr[1].shape[0] // cfg.seq_len)
+            for card in set(getattr(cfg, "temp_set", None) or [2]):      # the TRX heads' padded layout (shot * tuples no multiple of 4: 1-shot at 12 frames)
+                slots = ops._trx_class_slots(plan.counts, math.comb(cfg.seq_len, card))
+                if slots != plan.counts:
+                    plan.padded_rowmap(pr[2].shape[0] + pr[3].shape[0], slots)
             plans.append(plan)
         ops.refresh_packs([ops.side_stream(cfg.device), ops.aux_stream(cfg.device)] + ops.forked_streams(roles=("wgrad",)))
         slots = ops.SeedSlots(cfg.device, n=16 * len(prepared))
